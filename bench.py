@@ -13,7 +13,10 @@ hash); pings cross GPUs through the RCCL
 exchange. value = delivered messages over all ranks / max-over-ranks time of
 the K timed steps.
 
-Also reported on the same line:
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times the K
+steps and prints the result line. Its `atomics` and `roofline` fields are
+arithmetic on the counters and the two HIP events of those same K steps; they
+take no run of their own:
   roofline     — k_step's algorithmic HBM bytes per launch (SURVEY §8 d3:
                  2 x 16-B record per message + (2S + 2M) per active actor,
                  S = 24 B pinger state, M = 8 B mailbox head/tail) / its
@@ -22,7 +25,9 @@ Also reported on the same line:
                  boundaries, so it never exceeds ms_per_step); `traffic` =
                  HBM bytes per launch from the rocprofv3 --pmc passes of the
                  SAME libgpuactor.so (profiles/pmc_k_step_<tag>.json carries
-                 the library's sha256; null if none matches);
+                 the library's sha256; null if none matches).
+`--dump-outputs DIR` writes what the last timed step left (dump_outputs below).
+`--full` adds the legs that take runs of their own (null without it):
   cpu_baseline — the reference runtime (oracle/_ref/libponyrt.so, built from
                  KittyMac/ponyc src/libponyrt) running the same pinger graph
                  (oracle/_ref/harness_ubench) on this host: at every usable
@@ -44,6 +49,7 @@ set up the run fails (non-zero exit) unless the host-staged exchange is asked
 for with --host-transport or PONYC_AMD_SAME_GPU=1 (every rank on device 0, a
 rehearsal of the N-rank path on a one-GPU box; `config.ranks_share_gpu`).
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--actors A]
+                        [--dump-outputs DIR] [--full]
 """
 from __future__ import annotations
 
@@ -78,8 +84,13 @@ def parse():
     p.add_argument("--actors", type=int, default=1 << 20, help="pingers per GPU")
     p.add_argument("--initial", type=int, default=5)
     p.add_argument("--mailbox-cap", type=int, default=16)
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-ring", action="store_true")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the pingers' state and the counters "
+                        "as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the C1 ring leg and the reference CPU baselines (N=1)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU legs")
+    p.add_argument("--no-ring", action="store_true", help="--full without the ring leg")
     p.add_argument("--cpu-budget", type=int, default=10,
                    help="forward budget per pinger of the bounded CPU sample")
     p.add_argument("--cpu-runs", type=int, default=5)
@@ -366,6 +377,36 @@ def ring_gpu(reps: int = 3) -> dict:
             "dropped": dropped, "runs": [round(o[0], 1) for o in out]}
 
 
+# ---- --dump-outputs ---------------------------------------------------------------------
+DUMP_MAX_BYTES = 60_000_000     # per run, all ranks together (1M pingers fit: 56 B each)
+COUNT_KEYS = ("steps", "delivered", "sent", "pending", "dropped", "remote", "active")
+
+
+def dump_outputs(eng, ty: int, out_dir: str, rank: int, world: int) -> None:
+    """What a caller of the timed path holds after its last step: the pingers'
+    state (state_read: rng x, rng y, ping count; u64[3, local pingers]) and the
+    engine's counters. float64 holds 53 bits, so each u64 word is written as
+    its two 32-bit halves, both exact: state_hi.npy and state_lo.npy,
+    float64[3, n]. Past DUMP_MAX_BYTES the pingers are a fixed seeded sample,
+    whose local indices are state_index.npy. Rank r > 0 writes <name>_rank<r>.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = "" if rank == 0 else f"_rank{rank}"
+    st = eng.state_read(ty)
+    n = st.shape[1]
+    keep = DUMP_MAX_BYTES // world // (st.shape[0] * 2 * 8 + 8)
+    idx = np.arange(n, dtype=np.int64)
+    if n > keep:
+        idx = np.sort(np.random.default_rng(20240229).choice(n, size=keep, replace=False))
+        st = st[:, idx]
+    np.save(os.path.join(out_dir, f"state_hi{sfx}.npy"), (st >> np.uint64(32)).astype(np.float64))
+    np.save(os.path.join(out_dir, f"state_lo{sfx}.npy"),
+            (st & np.uint64(0xFFFFFFFF)).astype(np.float64))
+    np.save(os.path.join(out_dir, f"state_index{sfx}.npy"), idx.astype(np.float64))
+    c = eng.counts()
+    np.save(os.path.join(out_dir, f"counts{sfx}.npy"),
+            np.array([c[k] for k in COUNT_KEYS], dtype=np.float64))
+
+
 def main():
     args = parse()
     if args.gpus < 1:
@@ -440,6 +481,8 @@ def main():
     active = c1["active"] - c0["active"]
     atomics = c1["atomics"] - c0["atomics"]
     dropped = c1["dropped"]
+    if args.dump_outputs:
+        dump_outputs(eng, ty, args.dump_outputs, rank, world)
     eng.shutdown()
 
     # roofline of the step kernel on this rank (per launch)
@@ -453,7 +496,7 @@ def main():
     traffic, traffic_src = pmc_traffic(sha)
 
     cpu = ring = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         if not args.no_ring:
             ring = {"workload": "C1 examples/ring --size 1000 --count 100 --pass 10000 "
                                 "(100,000 actors, 1,000,100 pass + 100 set messages), run to "

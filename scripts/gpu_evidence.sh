@@ -23,8 +23,9 @@ if [ -z "$PART" ] || [ "$PART" = A ]; then
   timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke_$TAG.log 2>&1 || exit $?
   tail -3 gpurun_out/smoke_$TAG.log
   if [ -z "$SKIP_FULL_BENCH" ]; then
-    timeout -k 10 600 python bench.py > gpurun_out/bench_full_$TAG.json 2> gpurun_out/bench_full_$TAG.err || exit $?
-    cat gpurun_out/bench_full_$TAG.json
+    mkdir -p "${RESULTS_DIR:=results}"
+    timeout -k 10 600 python bench.py --full > "$RESULTS_DIR"/bench_full_$TAG.json 2> "$RESULTS_DIR"/bench_full_$TAG.err || exit $?
+    cat "$RESULTS_DIR"/bench_full_$TAG.json
   fi
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof/$TAG -o run -- \
     python3 bench.py --no-cpu-baseline --no-ring > gpurun_out/prof_bench_$TAG.json 2> gpurun_out/prof_$TAG.err || exit $?
