@@ -92,7 +92,8 @@ typedef struct gpu_actor_counts_t
   uint64_t sent;        /* application messages emitted by handlers          */
   uint64_t pending;     /* messages waiting in mailboxes now                 */
   uint64_t dropped;     /* messages lost to mailbox overflow (error)          */
-  uint64_t remote;      /* messages that crossed ranks                       */
+  uint64_t remote;      /* messages that crossed ranks (GUPS updates of a    */
+                        /* peer's chunk applied here count as such)          */
   uint64_t active;      /* actor-steps that handled at least one message     */
   uint64_t delivered_by_type[GPU_ACTOR_MAX_TYPES];
   uint64_t atomics;     /* global chunk-reservation atomics the drain kernel

@@ -350,6 +350,14 @@ struct Engine {
   uint64_t gups_jump_host[65] = {};
   uint32_t gups_cap = 0;
   int gups_type = -1;
+  // n_ranks > 1: this rank's chunks packed to one run (k_gups_pack), every
+  // rank's runs gathered in rank order for k_gups_apply_ranks; chunks received
+  // from peers and listed here since init (gpu_actor_debug_info)
+  uint64_t* d_gups_send = nullptr;
+  uint64_t* d_gups_all = nullptr;
+  uint64_t gups_all_cap = 0;
+  uint32_t gups_parts = 0;
+  uint64_t gups_in_total = 0, gups_out_total = 0;
   // One rank: device work that can change the spill status or the counters
   // bumps dev_epoch; a host read of either records the epoch it saw, so a
   // read that nothing could have changed since is skipped (run_fixed's and
@@ -362,7 +370,9 @@ struct Engine {
   ncclComm_t comm = nullptr;
   XRec* d_xout = nullptr;
   XRec* d_xin = nullptr;
-  unsigned long long* d_xc = nullptr;      // [2R + 2]: send counts, receive counts, scratch
+  // [3R + 3]: send counts, receive counts, two scratch words, the GUPS chunks
+  // this rank listed in the step (k_gups_pack), every rank's such count
+  unsigned long long* d_xc = nullptr;
   unsigned long long* d_xcount = nullptr;  // d_xc
   unsigned long long* d_xrecv = nullptr;   // d_xc + R
   unsigned long long* h_xc = nullptr;      // pinned mirror of d_xc
@@ -558,18 +568,24 @@ bool hot_resident()
 }
 
 constexpr uint32_t kGupsBlocks = 1024;
+constexpr uint32_t kGupsPackBlocks = 256;
 __global__ void __launch_bounds__(256) k_gups_apply();
+__global__ void __launch_bounds__(256) k_gups_pack(uint64_t* out, unsigned long long* count);
+__global__ void __launch_bounds__(256) k_gups_apply_ranks(const uint64_t* list, uint64_t n,
+  uint64_t own_lo, uint64_t own_n);
 
 // The GUPS streamer type whose chunks k_gups_apply makes (EngDev::gups_*): the
-// first with a nonzero chunk, on one rank (PONYC_AMD_GUPS_DEFER=0: none, every
-// streamer applies its own chunk, for A/B runs). Chunks of L >= 16 updates per
-// lane, at most 64 lanes per chunk.
+// first with a nonzero chunk, at any rank count (PONYC_AMD_GUPS_DEFER=0: none,
+// every streamer applies its own chunk, for A/B runs; the ranks of one engine
+// must agree on it, as on every setting). Chunks of L >= 16 updates per lane,
+// at most 64 lanes per chunk. With n_ranks > 1 the listed chunks are packed,
+// gathered by every rank and applied by k_gups_apply_ranks (gups_gather_apply).
 int gups_setup(EngDev& e)
 {
   g.gups_type = -1;
   e.gups_type = -1;
   const char* f = getenv("PONYC_AMD_GUPS_DEFER");
-  if(R() != 1 || (f && atoi(f) == 0)) return 0;
+  if(f && atoi(f) == 0) return 0;
   int t_def = -1;
   for(uint32_t t = 0; t < GPU_ACTOR_MAX_TYPES && t_def < 0; ++t)
     if(g.types[t].created && g.types[t].ht == GPU_ACTOR_HT_GUPS_STREAMER && g.types[t].params[0] > 0 &&
@@ -591,14 +607,19 @@ int gups_setup(EngDev& e)
     g.gups_cap = 0;
     HIPCK(hipMalloc(&g.d_gups_list, cap * sizeof(uint64_t)));
     g.gups_cap = (uint32_t)cap;
+    // the packed run holds what the list holds (between steps both are empty)
+    if(g.d_gups_send) HIPCK(hipFree(g.d_gups_send));
+    g.d_gups_send = nullptr;
   }
+  if(R() > 1 && !g.d_gups_send)
+    HIPCK(hipMalloc(&g.d_gups_send, (size_t)g.gups_cap * sizeof(uint64_t)));
   if(!g.d_gups_n)
   {
     HIPCK(hipMalloc(&g.d_gups_n, (kGupsShards + 1) * sizeof(unsigned int)));
     HIPCK(hipMemsetAsync(g.d_gups_n, 0, (kGupsShards + 1) * sizeof(unsigned int), g.stream));
     HIPCK(hipMalloc(&g.d_gups_jump, 65 * sizeof(uint64_t)));
-    HIPCK(hipMalloc(&g.d_gups_stat, 2 * kGupsBlocks * sizeof(unsigned long long)));
-    HIPCK(hipMemsetAsync(g.d_gups_stat, 0, 2 * kGupsBlocks * sizeof(unsigned long long), g.stream));
+    HIPCK(hipMalloc(&g.d_gups_stat, 3 * kGupsBlocks * sizeof(unsigned long long)));
+    HIPCK(hipMemsetAsync(g.d_gups_stat, 0, 3 * kGupsBlocks * sizeof(unsigned long long), g.stream));
   }
   uint64_t jump[65] = {};
   for(uint64_t p = 0; p < parts; ++p) jump[p] = gpa::polyrand_xpow(p * L);
@@ -622,14 +643,16 @@ int gups_setup(EngDev& e)
   e.gups_l = (uint32_t)L; e.gups_parts = (uint32_t)parts;
   e.gups_type = t_def;
   g.gups_type = t_def;
+  g.gups_parts = (uint32_t)parts;
   return 0;
 }
 
 // k_gups_apply behind a step's kernels (engines with a chunk-listing streamer
-// type); the events, when given, end at its end
+// type, one rank; with more the chunks are applied after the exchange,
+// gups_gather_apply); the events, when given, end at its end
 int gups_apply_launch(hipEvent_t e1)
 {
-  if(g.gups_type < 0) return 0;
+  if(g.gups_type < 0 || R() > 1) return 0;
   if(e1)
     hipExtLaunchKernelGGL(k_gups_apply, dim3(kGupsBlocks), dim3(256), 0, g.stream, nullptr, e1, 0u);
   else
@@ -1267,6 +1290,142 @@ __global__ void __launch_bounds__(256) k_gups_apply()
   }
 }
 
+// n_ranks > 1: the chunks this rank's streamers listed in the step, packed in
+// segment order to out[0 .. *count) — the run every peer receives — with the
+// prefix k_gups_apply builds. The last workgroup to finish empties the list.
+__global__ void __launch_bounds__(256) k_gups_pack(uint64_t* out, unsigned long long* count)
+{
+  __shared__ uint32_t s_pre[kGupsShards + 1];
+  if(threadIdx.x < kGupsShards)
+  {
+    uint32_t c = min(__atomic_load_n(&c_eng.gups_n[threadIdx.x], __ATOMIC_RELAXED), c_eng.gups_seg);
+    for(int off = 1; off < (int)kGupsShards; off <<= 1)
+    {
+      const uint32_t o = __shfl_up(c, off);
+      if((int)threadIdx.x >= off) c += o;
+    }
+    s_pre[threadIdx.x + 1] = c;
+    if(threadIdx.x == 0) s_pre[0] = 0;
+  }
+  __syncthreads();
+  const uint32_t n = s_pre[kGupsShards];
+  for(uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n;
+      e += (uint64_t)gridDim.x * blockDim.x)
+  {
+    uint32_t lo = 0, hi = kGupsShards;
+    while(hi - lo > 1u)
+    {
+      const uint32_t mid = (lo + hi) >> 1;
+      if(s_pre[mid] <= e) lo = mid; else hi = mid;
+    }
+    out[e] = c_eng.gups_list[(size_t)lo * c_eng.gups_seg + (e - s_pre[lo])];
+  }
+  if(threadIdx.x == 0)
+  {
+    if(blockIdx.x == 0) *count = n;
+    const unsigned int done = atomicAdd(&c_eng.gups_n[kGupsShards], 1u);
+    if(done == gridDim.x - 1u)
+      for(uint32_t s = 0; s <= kGupsShards; ++s) atomicExch(&c_eng.gups_n[s], 0u);
+  }
+}
+
+// k_gups_apply for n_ranks > 1: list[0 .. n) holds every rank's chunks of the
+// step in rank order (gups_gather_apply), this rank's own at [own_lo, own_lo +
+// own_n). Every rank regenerates every chunk, lane p from state * x^(p * L) as
+// above, and keeps the updates whose updater it owns (is_remote), addressed
+// through the owner-local slot; the wave's same-word combine and the skipped
+// XOR of 0 are k_gups_apply's. gups_stat counts the kept updates, their
+// atomics, and (third row) the kept updates of peers' chunks: the updates a
+// record per update would have carried across ranks.
+__global__ void __launch_bounds__(256) k_gups_apply_ranks(const uint64_t* list, uint64_t n,
+  uint64_t own_lo, uint64_t own_n)
+{
+  const TypeDev& S = c_types[c_eng.gups_type];
+  const uint64_t chunk = S.params[0], shift = S.params[1], mask = S.params[2];
+  const uint32_t ubase = (uint32_t)S.params[3];
+  const uint32_t L = c_eng.gups_l, parts = c_eng.gups_parts, per_wave = 64u / parts;
+  const uint32_t lane = threadIdx.x & 63u, sub = lane / parts, p = lane - sub * parts;
+  const uint64_t jump = c_eng.gups_jump[p];
+  const uint64_t first = (uint64_t)p * L;
+  const uint32_t cnt = first < chunk ? (uint32_t)min<uint64_t>(L, chunk - first) : 0u;
+  const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+  uint32_t u_first = 0, u_count = 0, u_lfirst = 0, u_lcount = 0;
+  uint64_t* u_state = nullptr;
+  uint64_t u_mask = 0;
+  uint32_t made = 0, issued = 0, far = 0;
+  for(uint64_t e0 = wave * per_wave; e0 < n; e0 += waves * per_wave)
+  {
+    const uint64_t e = e0 + sub;
+    const bool live = sub < per_wave && e < n;
+    const uint32_t peer = e - own_lo >= own_n ? 1u : 0u;
+    uint64_t v = live ? list[e] : 0ull;
+    if(live && p) v = polyrand_mulmod(v, jump);
+    for(uint32_t j = 0; j < L; ++j)
+    {
+      unsigned long long* w = nullptr;
+      if(live && j < cnt)
+      {
+        (void)polyrand_next(v);
+        const uint32_t to = ubase + (uint32_t)((v >> shift) & mask);
+        if(!is_remote(to))
+        {
+          ++made;
+          far += peer;
+          if(to - u_first >= u_count)
+          {
+            const int t = type_of_global(to);
+            if(t >= 0)
+            {
+              const TypeDev& U = c_types[t];
+              u_first = U.first; u_count = U.count; u_lfirst = U.lfirst; u_lcount = U.lcount;
+              u_state = U.state; u_mask = U.params[0] - 1;
+            }
+          }
+          if(to - u_first < u_count)
+            w = reinterpret_cast<unsigned long long*>(
+              &u_state[(v & u_mask) * u_lcount + (rdiv(to) - u_lfirst)]);
+        }
+      }
+      const uint64_t wa = reinterpret_cast<uint64_t>(w);
+      uint64_t left = __ballot(w != nullptr);
+      for(int round = 0; round < 2 && left; ++round)
+      {
+        const uint32_t lead = (uint32_t)__ffsll((long long)left) - 1u;
+        const uint64_t lw = __shfl(wa, (int)lead);
+        const uint64_t peers = __ballot(((left >> lane) & 1ull) && wa == lw);
+        uint64_t r = ((peers >> lane) & 1ull) ? v : 0ull;
+        if(__popcll(peers) > 1)
+          for(int off = 32; off; off >>= 1) r ^= __shfl_xor(r, off);
+        if(lane == lead && r != 0)
+        {
+          atomicXor(w, (unsigned long long)r);
+          ++issued;
+        }
+        left &= ~peers;
+      }
+      if(((left >> lane) & 1ull) && v != 0)
+      {
+        atomicXor(w, (unsigned long long)v);
+        ++issued;
+      }
+    }
+  }
+  __shared__ uint32_t s_sum[3];
+  if(threadIdx.x < 3) s_sum[threadIdx.x] = 0;
+  __syncthreads();
+  if(made) atomicAdd(&s_sum[0], made);
+  if(issued) atomicAdd(&s_sum[1], issued);
+  if(far) atomicAdd(&s_sum[2], far);
+  __syncthreads();
+  if(threadIdx.x == 0)
+  {
+    c_eng.gups_stat[blockIdx.x] += s_sum[0];
+    c_eng.gups_stat[kGupsBlocks + blockIdx.x] += s_sum[1];
+    c_eng.gups_stat[2 * kGupsBlocks + blockIdx.x] += s_sum[2];
+  }
+}
+
 __global__ void k_spill_local(unsigned long long* out)
 {
   *out = (unsigned long long)c_eng.spill_n[0] + c_eng.spill_n[1] + *c_eng.halt +
@@ -1668,8 +1827,20 @@ int exchange_step(uint32_t step_sidx)
   if(rc) return rc;
   rc = xc_allreduce_sum(g.d_trig_n + tslot, g.d_trig_n + tslot, 1, XC_U32);
   if(rc) return rc;
+  // the GUPS chunks listed in the step, packed, and every rank's count of
+  // them (the chunks themselves move after the halt check: gups_gather_apply)
+  if(g.gups_type >= 0)
+  {
+    hipLaunchKernelGGL(k_gups_pack, dim3(kGupsPackBlocks), dim3(256), 0, g.stream, g.d_gups_send,
+      g.d_xc + 2 * n + 2);
+    HIPCK(hipGetLastError());
+    rc = xc_allgather_u64(g.d_xc + 2 * n + 2, g.d_xc + 2 * n + 3);
+    if(rc) return rc;
+    HIPCK(hipMemcpyAsync(g.h_xc + 2 * n + 2, g.d_xc + 2 * n + 2, (n + 1) * sizeof(unsigned long long),
+      hipMemcpyDeviceToHost, g.stream));
+  }
   // the step's one readback: send and receive counts, trigger count, kept
-  // exchange-spill records, spill status
+  // exchange-spill records, spill status, GUPS chunk counts
   g.h_xc[2 * n] = 0;
   g.h_xc[2 * n + 1] = 0;
   HIPCK(hipMemcpyAsync(g.h_xc, g.d_xc, 2 * n * sizeof(unsigned long long), hipMemcpyDeviceToHost,
@@ -2018,7 +2189,9 @@ int launch_step(uint32_t slot, hipEvent_t e0, hipEvent_t e1)
       hipLaunchKernelGGL(k_carry_big, dim3(kBigCopyBlocks), dim3(kBlock), 0, g.stream, g.par);
     const int grc = gups_apply_launch(nullptr);
     if(grc) return grc;
-    if(e1) HIPCK(hipEventRecord(e1, g.stream));
+    // (n_ranks > 1 with listed GUPS chunks: the end event goes behind their
+    // apply, gups_gather_apply)
+    if(e1 && !(g.gups_type >= 0 && R() > 1)) HIPCK(hipEventRecord(e1, g.stream));
     return step_after_launch(slot, e0, e1);
   }
   // a two-pass table's step as two launches: its two-pass zones, then the rest
@@ -2032,7 +2205,8 @@ int launch_step(uint32_t slot, hipEvent_t e0, hipEvent_t e1)
   if(e0)
   {
     // the events take the dispatch's own start/end timestamps: no marker
-    // packets between steps
+    // packets between steps (the chunks' apply ends them: the next launch
+    // here on one rank, gups_gather_apply's after the exchange otherwise)
     const bool gups = g.gups_type >= 0;
     const bool more = split || g.defer_big || gups;
     if(g.hot_on)
@@ -2067,8 +2241,77 @@ int launch_step(uint32_t slot, hipEvent_t e0, hipEvent_t e1)
   return step_after_launch(slot, e0, e1);
 }
 
+// n_ranks > 1, behind a step that ran: every rank's packed GUPS chunks
+// (k_gups_pack; the counts are on the host since exchange_step's readback)
+// gathered in rank order — one 8-byte PolyRand state per chunk, through the
+// grouped send/recv that gathers spawn records — and applied by
+// k_gups_apply_ranks. A rank that owns no updater takes part in the gather
+// and launches nothing. The step's end event, when given, ends here.
+int gups_gather_apply(hipEvent_t e1)
+{
+  const uint32_t n = R();
+  const unsigned long long* cnt = g.h_xc + 2 * n + 3;
+  std::vector<uint64_t> off(n);
+  uint64_t total = 0;
+  for(uint32_t p = 0; p < n; ++p)
+  {
+    off[p] = total;
+    total += cnt[p];
+  }
+  const uint64_t mine = cnt[rank()];
+  g.gups_out_total += mine;
+  g.gups_in_total += total - mine;
+  if(total > g.gups_all_cap)
+  {
+    const uint64_t cap = std::max<uint64_t>({2ull * g.gups_all_cap, total + total / 2, 1ull << 16});
+    HIPCK(hipStreamSynchronize(g.stream));      // no k_gups_apply_ranks still reads the old one
+    if(g.d_gups_all) HIPCK(hipFree(g.d_gups_all));
+    g.d_gups_all = nullptr;
+    g.gups_all_cap = 0;
+    HIPCK(hipMalloc(&g.d_gups_all, cap * sizeof(uint64_t)));
+    g.gups_all_cap = cap;
+  }
+  bool launched = false;
+  if(total)
+  {
+    if(mine)
+      HIPCK(hipMemcpyAsync(g.d_gups_all + off[rank()], g.d_gups_send, mine * sizeof(uint64_t),
+        hipMemcpyDeviceToDevice, g.stream));
+    std::vector<XcPeer> pp(n);
+    for(uint32_t p = 0; p < n; ++p)
+    {
+      if(p == rank()) continue;
+      pp[p].d_send = g.d_gups_send;
+      pp[p].send = mine * sizeof(uint64_t);
+      pp[p].d_recv = g.d_gups_all + off[p];
+      pp[p].recv = cnt[p] * sizeof(uint64_t);
+    }
+    const int rc = xc_sendrecv(pp);
+    if(rc) return rc;
+    // the updaters the streamers write: ids ubase .. ubase + mask
+    const HostType& h = g.types[g.gups_type];
+    const uint64_t u0 = h.params[3], u1 = u0 + h.params[2] + 1;
+    if(owned_below(u1) > owned_below(u0))
+    {
+      const uint64_t per_block = 4ull * (64u / g.gups_parts);
+      const uint32_t blocks = (uint32_t)std::min<uint64_t>((total + per_block - 1) / per_block, kGupsBlocks);
+      if(e1)
+        hipExtLaunchKernelGGL(k_gups_apply_ranks, dim3(blocks), dim3(256), 0, g.stream, nullptr, e1, 0u,
+          (const uint64_t*)g.d_gups_all, total, off[rank()], mine);
+      else
+        hipLaunchKernelGGL(k_gups_apply_ranks, dim3(blocks), dim3(256), 0, g.stream,
+          (const uint64_t*)g.d_gups_all, total, off[rank()], mine);
+      HIPCK(hipGetLastError());
+      launched = true;
+    }
+  }
+  if(e1 && !launched) HIPCK(hipEventRecord(e1, g.stream));
+  return 0;
+}
+
 // After a step's launches: the parity and step index advance; the exchange
-// (n_ranks > 1), the halted step's rerun, spawned actors.
+// (n_ranks > 1), the halted step's rerun, the GUPS chunks' gather and apply
+// (n_ranks > 1), spawned actors.
 int step_after_launch(uint32_t slot, hipEvent_t e0, hipEvent_t e1)
 {
   HIPCK(hipGetLastError());
@@ -2090,6 +2333,11 @@ int step_after_launch(uint32_t slot, hipEvent_t e0, hipEvent_t e1)
       rc = pend_clear(slot, 1);
       if(rc) return rc;
       return launch_step(slot, e0, e1);
+    }
+    if(g.gups_type >= 0)
+    {
+      rc = gups_gather_apply(e1);
+      if(rc) return rc;
     }
   }
   if(g.spawn_cap)
@@ -2128,6 +2376,21 @@ int pend_read(uint32_t first, uint32_t n, std::vector<unsigned long long>& out)
   return 0;
 }
 
+// k_gups_apply's (n_ranks > 1: k_gups_apply_ranks') per-workgroup counts
+// summed: updates made, atomics issued, updates of peers' chunks.
+int gups_stat_read(uint64_t out[3])
+{
+  out[0] = out[1] = out[2] = 0;
+  if(!g.d_gups_stat) return 0;
+  std::vector<unsigned long long> st(3 * kGupsBlocks);
+  HIPCK(hipMemcpyAsync(st.data(), g.d_gups_stat, st.size() * sizeof(unsigned long long),
+    hipMemcpyDeviceToHost, g.stream));
+  HIPCK(hipStreamSynchronize(g.stream));
+  for(uint32_t b = 0; b < kGupsBlocks; ++b)
+    for(int k = 0; k < 3; ++k) out[k] += st[(size_t)k * kGupsBlocks + b];
+  return 0;
+}
+
 int ensure_events(size_t n)
 {
   while(g.ev.size() < n)
@@ -2149,6 +2412,10 @@ void free_all()
   if(g.d_gups_n) (void)hipFree(g.d_gups_n);
   if(g.d_gups_jump) (void)hipFree(g.d_gups_jump);
   if(g.d_gups_stat) (void)hipFree(g.d_gups_stat);
+  if(g.d_gups_send) (void)hipFree(g.d_gups_send);
+  if(g.d_gups_all) (void)hipFree(g.d_gups_all);
+  g.d_gups_send = nullptr; g.d_gups_all = nullptr;
+  g.gups_all_cap = 0; g.gups_parts = 0; g.gups_in_total = g.gups_out_total = 0;
   g.d_gups_list = nullptr; g.d_gups_n = nullptr; g.d_gups_jump = nullptr; g.d_gups_stat = nullptr;
   memset(g.gups_jump_host, 0, sizeof(g.gups_jump_host));
   g.gups_cap = 0;
@@ -2426,9 +2693,9 @@ GPU_ACTOR_API int gpu_actor_init(const gpu_actor_config_t* cfg)
       const int xrc = alloc_xspill(std::max<uint32_t>(1u << 18, g.xcap / 2));
       if(xrc) return xrc;
     }
-    HIPCK(hipMalloc(&g.d_xc, (2 * R() + 2) * sizeof(unsigned long long)));
-    HIPCK(hipMemsetAsync(g.d_xc, 0, (2 * R() + 2) * sizeof(unsigned long long), g.stream));
-    HIPCK(hipHostMalloc(&g.h_xc, (2 * R() + 2) * sizeof(unsigned long long), hipHostMallocDefault));
+    HIPCK(hipMalloc(&g.d_xc, (3 * R() + 3) * sizeof(unsigned long long)));
+    HIPCK(hipMemsetAsync(g.d_xc, 0, (3 * R() + 3) * sizeof(unsigned long long), g.stream));
+    HIPCK(hipHostMalloc(&g.h_xc, (3 * R() + 3) * sizeof(unsigned long long), hipHostMallocDefault));
     g.d_xcount = g.d_xc;
     g.d_xrecv = g.d_xc + R();
     g.h_xcount.assign(R(), 0);
@@ -3178,7 +3445,10 @@ GPU_ACTOR_API int gpu_actor_counts(gpu_actor_counts_t* out)
   }
   if(!out) return GPU_ACTOR_EINVAL;
   unsigned long long st[ST_COUNT];
-  int rc = pend_clear(kPendPre, 1);
+  uint64_t gu[3] = {0, 0, 0};
+  int rc = R() > 1 ? gups_stat_read(gu) : 0;
+  if(rc) return rc;
+  rc = pend_clear(kPendPre, 1);
   if(rc) return rc;
   rc = fold_counters(0, 0);
   if(rc) return rc;
@@ -3205,7 +3475,8 @@ GPU_ACTOR_API int gpu_actor_counts(gpu_actor_counts_t* out)
   out->sent = st[ST_SENT];
   out->pending = pend;
   out->dropped = st[ST_DROPPED] + st[ST_XCHG_OVERFLOW];
-  out->remote = g.remote_total;
+  // + the updates k_gups_apply_ranks applied here from peers' chunks
+  out->remote = g.remote_total + gu[2];
   out->active = st[ST_ACTIVE];
   for(int t = 0; t < GPU_ACTOR_MAX_TYPES; ++t) out->delivered_by_type[t] = st[ST_BY_TYPE + t];
   out->atomics = st[ST_ATOMICS];
@@ -3248,20 +3519,21 @@ GPU_ACTOR_API int gpu_actor_debug_info(uint64_t* out, uint64_t n)
   // + [12] whether the last step ran the module compiled from the programs
   // (jit_host.h), [13] modules built or loaded by this engine
   // + [14] updates k_gups_apply made, [15] the atomics it issued for them
-  uint64_t gu[2] = {0, 0};
-  if(g.d_gups_stat)
+  // (n_ranks > 1: k_gups_apply_ranks', for the updaters this rank owns)
+  uint64_t gu[3] = {0, 0, 0};
   {
-    std::vector<unsigned long long> st(2 * kGupsBlocks);
-    HIPCK(hipMemcpyAsync(st.data(), g.d_gups_stat, st.size() * sizeof(unsigned long long),
-      hipMemcpyDeviceToHost, g.stream));
-    HIPCK(hipStreamSynchronize(g.stream));
-    for(uint32_t b = 0; b < kGupsBlocks; ++b) { gu[0] += st[b]; gu[1] += st[kGupsBlocks + b]; }
+    const int rc = gups_stat_read(gu);
+    if(rc) return rc;
   }
   // + [16] whether cross-rank records go straight into the peers' inboxes
-  const uint64_t v[17] = {g.fixups, g.sparse_launches, g.sparse_steps, g.zone_records, g.spill_cap,
+  // + [17] GUPS chunk descriptors received from peers, [18] listed by this
+  // rank (n_ranks > 1), [19] this rank's share of gpu_actor_counts' remote
+  // from k_gups_apply_ranks: the updates of peers' chunks it applied
+  const uint64_t v[20] = {g.fixups, g.sparse_launches, g.sparse_steps, g.zone_records, g.spill_cap,
                           g.n_zones, tn[0], tn[1], tn[2], g.zbits, hb[3], g.hot_on ? 1u : 0u,
-                          g.jit_used ? 1u : 0u, g.jit_builds, gu[0], gu[1], g.peer_write ? 1u : 0u};
-  for(uint64_t i = 0; i < n && i < 17; ++i) out[i] = v[i];
+                          g.jit_used ? 1u : 0u, g.jit_builds, gu[0], gu[1], g.peer_write ? 1u : 0u,
+                          g.gups_in_total, g.gups_out_total, gu[2]};
+  for(uint64_t i = 0; i < n && i < 20; ++i) out[i] = v[i];
   return 0;
 }
 

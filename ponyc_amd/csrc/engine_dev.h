@@ -232,20 +232,25 @@ struct EngDev {
   uint32_t* hot_bcnt;
   uint32_t* hot_cur;
   uint32_t* hot_bar;
-  // GUPS streamers' chunks handed to the whole GPU (one rank, DESIGN.md §7
-  // C4): a streamer of type gups_type (-1: none) lists its PolyRand state
+  // GUPS streamers' chunks handed to the whole GPU:
+  // a streamer of type gups_type (-1: none) lists its PolyRand state
   // before the chunk in gups_list and moves past the chunk with one jump
   // (gups_jump[gups_parts] = x^chunk); k_gups_apply, launched behind every
   // step, regenerates each chunk over gups_parts lanes, lane p from state *
-  // gups_jump[p] (= x^(p * gups_l)), and applies it. The list is kGupsShards
+  // gups_jump[p] (= x^(p * gups_l)), and applies it. With n_ranks > 1 the
+  // listed states are packed (k_gups_pack), gathered by every rank, and
+  // k_gups_apply_ranks applies of every rank's chunks the updates whose
+  // updater this rank owns. The list is kGupsShards
   // segments of gups_seg chunks, a wave listing into segment (its global wave
   // index mod kGupsShards): one counter for 16,384 listing waves per step
   // serialised at the memory-side atomic unit (~13 ns each, 210 us of a C4
   // wide step). gups_n: [s] chunks listed in segment s (past gups_seg a
-  // streamer applies its chunk itself), [kGupsShards] finished k_gups_apply
-  // workgroups. gups_stat: per k_gups_apply workgroup, updates generated and
-  // atomics issued (an update whose XOR operand is 0 changes no word and is
-  // not issued; same-word updates of one wave are combined).
+  // streamer applies its chunk itself), [kGupsShards] finished workgroups of
+  // the kernel that empties the list (k_gups_apply; n_ranks > 1: k_gups_pack).
+  // gups_stat: per apply workgroup, updates generated and atomics issued (an
+  // update whose XOR operand is 0 changes no word and is not issued; same-word
+  // updates of one wave are combined), and with n_ranks > 1 the updates of
+  // peers' chunks among them.
   uint64_t* gups_list;
   unsigned int* gups_n;
   const uint64_t* gups_jump;
@@ -421,10 +426,11 @@ __device__ __forceinline__ void reducible_apply_local(uint32_t to, uint32_t beh,
         (unsigned long long)arg);
       break;
     case GPU_ACTOR_HT_GUPS_UPDATER: {
-      // t[d & m] ^= d
+      // t[d & m] ^= d (an XOR of 0 changes no word: no atomic)
       const uint64_t k = arg & (T.params[0] - 1);
-      atomicXor(reinterpret_cast<unsigned long long*>(&T.state[k * T.lcount + li]),
-        (unsigned long long)arg);
+      if(arg != 0)
+        atomicXor(reinterpret_cast<unsigned long long*>(&T.state[k * T.lcount + li]),
+          (unsigned long long)arg);
       break;
     }
     default:
@@ -692,17 +698,23 @@ __device__ __forceinline__ void send_updater(A& a, uint32_t to, uint64_t d)
     a.rc_state = T.state;
     a.rc_mask = T.params[0] - 1;
   }
-  // gups_basic Updater.apply: t[d & (size - 1)] ^= d, every update issued
-  // (the streamers' chunks on one rank go through k_gups_apply instead)
+  // gups_basic Updater.apply: t[d & (size - 1)] ^= d, but for an XOR of 0,
+  // which changes no word (a stream left at 0 repeats word 0 of updater 0,
+  // one serialised atomic per update). The path of a streamer whose list
+  // segment is full, or with PONYC_AMD_GUPS_DEFER=0: listed chunks go through
+  // k_gups_apply / k_gups_apply_ranks instead.
   const uint32_t li = rdiv(to) - a.rc_lfirst;
-  atomicXor(reinterpret_cast<unsigned long long*>(&a.rc_state[(d & a.rc_mask) * a.rc_lcount + li]),
-    (unsigned long long)d);
+  if(d != 0)
+    atomicXor(reinterpret_cast<unsigned long long*>(&a.rc_state[(d & a.rc_mask) * a.rc_lcount + li]),
+      (unsigned long long)d);
 }
 
-// A GUPS streamer's chunk handed to k_gups_apply: its PolyRand state before
-// the chunk listed (one list atomic per wave, on the wave's segment), the
-// chunk's updates counted as sent and applied here. False when the segment is
-// full: the streamer applies the chunk itself.
+// A GUPS streamer's chunk handed to k_gups_apply (n_ranks > 1: to every
+// rank's k_gups_apply_ranks): its PolyRand state before the chunk listed (one
+// list atomic per wave, on the wave's segment), the chunk's updates counted as
+// sent and applied here, on the streamer's rank, whichever rank applies them
+// (the counters are summed over ranks). False when the segment is full: the
+// streamer applies the chunk itself.
 template <class A>
 __device__ __forceinline__ bool gups_defer(A& a, uint64_t last, uint64_t chunk, uint32_t ubase)
 {
@@ -838,7 +850,7 @@ __device__ __forceinline__ void handle(HtTag<GPU_ACTOR_HT_GUPS_STREAMER>, const 
   const uint64_t chunk = T.params[0], shift = T.params[1], mask = T.params[2];
   const uint32_t ubase = (uint32_t)T.params[3];
   uint64_t last = s[0];
-  // one rank: the chunk goes to k_gups_apply, the state jumps past it
+  // the chunk goes to k_gups_apply (at any rank count), the state jumps past it
   if(a.type == c_eng.gups_type && gups_defer(a, last, chunk, ubase))
     last = polyrand_mulmod(last, c_eng.gups_jump[c_eng.gups_parts]);
   else
