@@ -341,12 +341,20 @@ GPU_ACTOR_API const char* gpu_actor_strerror(int code);
  * message. state: 8 words. Registers r0-r7 are the state words, r8 the
  * message argument, r9 the actor's id, r10 the behaviour, r11-r15 zero at
  * entry; r0-r7 are the state afterwards. Words 0-15 of the program are the
- * entry index of behaviour 0-15's code (0: the behaviour does nothing); code
- * follows. An instruction is one u64:
+ * entry index of behaviour 0-15's code, taken modulo 2^32 (the word's low 32
+ * bits; 0: the behaviour does nothing — its message still counts as
+ * delivered); code follows. A message's behaviour selects entry
+ * (behaviour & 15). An instruction is one u64:
  *   op | d << 8 | a << 12 | b << 16 | (uint32_t)imm << 32   (imm: int32)
- * and pc indexes the next instruction while one runs. A behaviour ends at
- * HALT, at an invalid op or pc, or after GPU_ACTOR_PROG_MAX_STEPS
- * instructions. SEND to an id past the world's ids is dropped (counted).   */
+ * and pc indexes the next instruction while one runs: a jump's pc += imm
+ * starts from the jump's own index + 1. Any pc in [0, n) runs the word there
+ * as an instruction, the entry words included; a pc outside — an entry or a
+ * jump target below 0 or at or past n — ends the behaviour. A behaviour ends
+ * at HALT, at an invalid op (above SPAWN; the words after it do not run) or
+ * pc, or after GPU_ACTOR_PROG_MAX_STEPS instructions, every instruction
+ * begun counting as one; r0-r7 as they stand then are the state. SEND to an
+ * id past the world's ids — compared as a full u64, nothing is truncated —
+ * is dropped (counted as dropped, not as sent).                             */
 #define GPU_ACTOR_HT_PROGRAM         12
 #define GPU_ACTOR_PROG_ENTRIES       16
 #define GPU_ACTOR_PROG_MAX_STEPS     4096
@@ -370,7 +378,11 @@ GPU_ACTOR_API const char* gpu_actor_strerror(int code);
 #define GPU_ACTOR_OP_JNZ    17  /* if r[a] != 0: pc += imm                    */
 #define GPU_ACTOR_OP_JMP    18  /* pc += imm                                  */
 #define GPU_ACTOR_OP_SEND   19  /* send behaviour (imm & 15), arg r[b], to r[a] */
-#define GPU_ACTOR_OP_MIX    20  /* r[d] = splitmix64 finaliser of r[a]        */
+#define GPU_ACTOR_OP_MIX    20  /* r[d] = splitmix64's output from state r[a]:
+                                   z = r[a] + 0x9e3779b97f4a7c15;
+                                   z = (z ^ z >> 30) * 0xbf58476d1ce4e5b9;
+                                   z = (z ^ z >> 27) * 0x94d049bb133111eb;
+                                   r[d] = z ^ z >> 31                          */
 #define GPU_ACTOR_OP_YIELD  21  /* end this actor's run after this behaviour  */
 #define GPU_ACTOR_OP_SPAWN  22  /* create an actor of type (imm & 0xFF) whose
                                    constructor behaviour (imm >> 8 & 15) gets

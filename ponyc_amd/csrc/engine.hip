@@ -3566,8 +3566,30 @@ GPU_ACTOR_API int gpu_actor_debug_jit_compile(const uint32_t* types, const uint6
   return 0;
 }
 
-// Diagnostic (not in the public header): the same for the any-mix step of a
-// mix of compiled tables (bit per table id, jit_host.h build_mix).
+// Diagnostic (not in the public header): the translation unit jit_host.h
+// generates for that program set (jit::unit_source, what hiprtc would
+// compile), NUL-terminated into buf[0, cap). Returns the text's length without
+// the NUL — when that is >= cap nothing is written: call again with more
+// room — or GPU_ACTOR_EINVAL. Needs no device.
+GPU_ACTOR_API int64_t gpu_actor_debug_jit_source(const uint32_t* types, const uint64_t* words,
+  const uint32_t* lens, uint32_t nprog, int z12, char* buf, uint64_t cap)
+{
+  if(!types || !words || !lens || nprog == 0 || nprog > GPU_ACTOR_MAX_TYPES) return GPU_ACTOR_EINVAL;
+  std::vector<jit::Prog> progs;
+  uint64_t off = 0;
+  for(uint32_t k = 0; k < nprog; ++k)
+  {
+    if(lens[k] <= GPU_ACTOR_PROG_ENTRIES || lens[k] > jit::kMaxWords) return GPU_ACTOR_EINVAL;
+    progs.push_back({types[k], std::vector<uint64_t>(words + off, words + off + lens[k])});
+    off += lens[k];
+  }
+  const std::string src = jit::unit_source(progs, z12 != 0);
+  if(buf && src.size() < cap) memcpy(buf, src.c_str(), src.size() + 1);
+  return (int64_t)src.size();
+}
+
+// Diagnostic (not in the public header): gpu_actor_debug_jit_compile for the
+// any-mix step of a mix of compiled tables (bit per table id, jit_host.h build_mix).
 GPU_ACTOR_API int gpu_actor_debug_jit_compile_mix(uint32_t mask, int z12, const char* arch)
 {
   if(mask == 0) return GPU_ACTOR_EINVAL;

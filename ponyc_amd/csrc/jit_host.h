@@ -82,7 +82,8 @@ inline std::string prog_function(const Prog& p)
   s += "  switch(beh & 15u)\n  {\n";
   for(uint32_t b = 0; b < GPU_ACTOR_PROG_ENTRIES; ++b)
   {
-    const uint64_t e = P[b];
+    // the entry word modulo 2^32, as the interpreters take it (include/gpu_actor.h)
+    const uint32_t e = (uint32_t)P[b];
     if(e != 0 && e < np) s += "    case " + std::to_string(b) + ": goto " + L + std::to_string(e) + ";\n";
   }
   s += "    default: goto " + L + "end;\n  }\n";

@@ -423,6 +423,26 @@ def jit_compile(progs, z12: bool = False, arch: str = "gfx950", lib_path: str | 
                                           len(progs), int(z12), arch.encode()))
 
 
+def jit_source(progs, z12: bool = False, lib_path: str | None = None) -> str:
+    """The translation unit csrc/jit_host.h generates for a program set
+    (`progs`: [(type id, words), ...]) — what hiprtc would compile — as text
+    (diagnostic export gpu_actor_debug_jit_source; needs no device)."""
+    lib = ctypes.CDLL(lib_path or LIB_PATH)
+    fn = lib.gpu_actor_debug_jit_source
+    fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int,
+                   ctypes.c_char_p, ctypes.c_uint64]
+    fn.restype = ctypes.c_int64
+    types = np.array([t for t, _ in progs], dtype=np.uint32)
+    words = np.concatenate([np.asarray(w, dtype=np.uint64) for _, w in progs])
+    lens = np.array([len(w) for _, w in progs], dtype=np.uint32)
+    args = (types.ctypes.data, words.ctypes.data, lens.ctypes.data, len(progs), int(z12))
+    n = fn(*args, None, 0)
+    _ck("gpu_actor_debug_jit_source", n)
+    buf = ctypes.create_string_buffer(n + 1)
+    _ck("gpu_actor_debug_jit_source", fn(*args, buf, n + 1))
+    return buf.value.decode()
+
+
 def jit_compile_mix(mask: int, z12: bool = False, arch: str = "gfx950", lib_path: str | None = None) -> None:
     """The same for the any-mix step of a mix of compiled tables (`mask`: bit
     per table id; gpu_actor_debug_jit_compile_mix)."""

@@ -18,6 +18,7 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 def sets():
     from ponyc_amd import program as P
     from test_program import edge_program
+    from prog_conformance import jit_units
     out = []
     for z12 in (False, True):
         out.append(([(0, P.ring_program())], z12))
@@ -29,6 +30,9 @@ def sets():
     # (test_spreader_after_other_types)
     for mask in ((1 << 1) | (1 << 9) | (1 << 10), (1 << 1) | (1 << 11) | (1 << 4)):
         out.append((mask, False))
+    # the conformance sets (tests/prog_conformance.py): three program sets and
+    # the ring + program mix, at both geometries
+    out += jit_units()
     return out
 
 
