@@ -910,7 +910,7 @@ uint32_t pick_zone_bits(uint64_t n)
   if(const char* f = getenv("PONYC_AMD_ZONE_BITS"))      // test hook: force a geometry
     return atoi(f) == 12 ? 12u : 11u;
   // 4096-actor zones while their bucket arrays fit the LDS beside the z12
-  // kernels' static LDS (~2,200 buckets; ~1,500 for the two-pass table's six
+  // kernels' static LDS (~2,200 buckets; ~1,500 for a dp table's six
   // arrays); past that, 2048-actor zones at one workgroup per CU
   return (nz11 + rb > 640 && step_fits(step_entry_for(true), nz12 + rb)) ? 12u : 11u;
 }
@@ -2161,8 +2161,9 @@ int launch_step(uint32_t slot, hipEvent_t e0, hipEvent_t e1)
   g.dev_epoch++;
   const StepEntry se = pick_step_entry();
   if(se.stub) return GPU_ACTOR_EINVAL;      // an experiment build without this table
-  // bucket arrays (4 x buckets; six for an order-free zone's two passes:
-  // zone_dev.h two_pass) and, for hot receivers, the sort's work area
+  // bucket arrays (4 x buckets — an order-free zone's two passes need no
+  // more: zone_dev.h two_pass; six for a message-local table's, dp_table)
+  // and, for hot receivers, the sort's work area
   const uint64_t nb = g.n_zones + (R() > 1 ? R() : 0);
   if(!step_fits(se, nb)) return GPU_ACTOR_ERANGE;    // more buckets than a workgroup's LDS holds
   const size_t dyn = step_dyn_bytes(se, nb);
@@ -3529,11 +3530,19 @@ GPU_ACTOR_API int gpu_actor_debug_info(uint64_t* out, uint64_t n)
   // + [17] GUPS chunk descriptors received from peers, [18] listed by this
   // rank (n_ranks > 1), [19] this rank's share of gpu_actor_counts' remote
   // from k_gups_apply_ranks: the updates of peers' chunks it applied
-  const uint64_t v[20] = {g.fixups, g.sparse_launches, g.sparse_steps, g.zone_records, g.spill_cap,
+  // + [20] zone steps that took the two-pass plan path (zone_dev.h two_pass)
+  unsigned long long st[ST_COUNT];
+  {
+    const int rc = fold_counters(0, 0);
+    if(rc) return rc;
+  }
+  HIPCK(hipMemcpyAsync(st, g.d_stats, sizeof(st), hipMemcpyDeviceToHost, g.stream));
+  HIPCK(hipStreamSynchronize(g.stream));
+  const uint64_t v[21] = {g.fixups, g.sparse_launches, g.sparse_steps, g.zone_records, g.spill_cap,
                           g.n_zones, tn[0], tn[1], tn[2], g.zbits, hb[3], g.hot_on ? 1u : 0u,
                           g.jit_used ? 1u : 0u, g.jit_builds, gu[0], gu[1], g.peer_write ? 1u : 0u,
-                          g.gups_in_total, g.gups_out_total, gu[2]};
-  for(uint64_t i = 0; i < n && i < 20; ++i) out[i] = v[i];
+                          g.gups_in_total, g.gups_out_total, gu[2], st[ST_PLAN_ZONES]};
+  for(uint64_t i = 0; i < n && i < 21; ++i) out[i] = v[i];
   return 0;
 }
 

@@ -51,6 +51,7 @@ enum Stat : int {
   ST_DELIVERED = 0, ST_SENT = 1, ST_DROPPED = 2, ST_REMOTE_OUT = 3, ST_REMOTE_IN = 4,
   ST_SEQ_OVERFLOW = 5, ST_XCHG_OVERFLOW = 6, ST_ACTIVE = 7,
   ST_ATOMICS = 8,        // global reservation atomics issued by k_step
+  ST_PLAN_ZONES = 9,     // zone steps that took the two-pass plan path (gpu_actor_debug_info)
   ST_BY_TYPE = 16, ST_COUNT = 32
 };
 
@@ -776,6 +777,11 @@ __device__ __forceinline__ void handle(HtTag<GPU_ACTOR_HT_RING>, const TypeDev& 
   }
 }
 
+// The argument every ping carries (examples/message-ubench/main.pony:283).
+// The two-pass path keeps it out of its LDS tile and puts it back where a
+// record leaves the workgroup (zone_dev.h plan_const_arg).
+constexpr uint64_t kPingerPingArg = 42;
+
 // examples/message-ubench/main.pony:265-286 (+ forward budget)
 template <class A>
 __device__ __forceinline__ void handle(HtTag<GPU_ACTOR_HT_PINGER>, const TypeDev& T, A& a,
@@ -785,7 +791,7 @@ __device__ __forceinline__ void handle(HtTag<GPU_ACTOR_HT_PINGER>, const TypeDev
   if(s[2] <= T.params[2])
   {
     const uint64_t k = rand_int(s[0], s[1], T.params[0]);
-    send_serial(a, (uint32_t)(T.params[1] + k), GPU_ACTOR_PINGER_PING, 42);
+    send_serial(a, (uint32_t)(T.params[1] + k), GPU_ACTOR_PINGER_PING, kPingerPingArg);
   }
 }
 

@@ -1148,12 +1148,35 @@ template <int HT> __host__ __device__ constexpr int plan_words()
 {
   if constexpr(HT >= 0 && two_pass<HT>()) return HT_Words<HT>::W; else return 1;
 }
+// The argument every send of a two-pass table carries, a compile-time
+// constant: pass 2's tile then holds 8-byte records {to, w | src_local}, and
+// the argument is put back where a record leaves the workgroup (TileCtx,
+// plan_emit). A table whose sends carry a run-time argument has no such
+// constant and does not take this path (dp keeps 16-byte tile records).
+template <int HT> __host__ __device__ constexpr uint64_t plan_const_arg()
+{
+  static_assert(HT == GPU_ACTOR_HT_PINGER, "only the pinger's sends carry a constant");
+  return kPingerPingArg;
+}
 constexpr uint32_t kRounds = kZone / kZoneThreads;
 static_assert(kRounds == 4, "two rounds per packed count word, two words");
 constexpr uint32_t kClasses = 16;   // message-count classes of the two-pass dealing (>= 15 share one)
 
-// pass 2's tile: the whole LDS pool (the per-actor counts are in registers by then)
-constexpr uint32_t kPlanTile = kTile;
+// pass 2's tile: the whole LDS pool (the per-actor counts are in registers by
+// then), in 8-byte records — two drain rounds (a super-round) of a zone at
+// once: 1024 actors' sends at Poisson(5) are 5120 +- 72 of 8192 places
+// (10240 +- 101 of 14336 with 4096-actor zones)
+constexpr uint32_t kPlanTile = kTile * (uint32_t)(sizeof(uint4) / sizeof(uint2));
+constexpr uint32_t kSuper = 2;                       // super-rounds of the plan path
+constexpr uint32_t kPerSuper = kRounds / kSuper;     // drain rounds (actors of a thread) in each
+
+// A tile record as it leaves the workgroup: a 16-byte one as it is, an 8-byte
+// one with the table's constant argument.
+__device__ __forceinline__ uint4 tile_rec16(const uint4& r, uint64_t) { return r; }
+__device__ __forceinline__ uint4 tile_rec16(const uint2& r, uint64_t arg)
+{
+  return make_uint4(r.x, r.y, (uint32_t)arg, (uint32_t)(arg >> 32));
+}
 
 // Store record r = {to, w | src_local, arg lo, arg hi} at position pos of
 // bucket b's chunk: a destination zone's landing buffer (past its capacity:
@@ -1233,10 +1256,13 @@ struct PlanCtx : ActorBase {
 };
 
 // pass 2: the send's rank in its bucket comes from the round's cursor; the
-// tile holds it at start + rank; past the tile it goes straight to its chunk
+// tile holds it at start + rank; past the tile it goes straight to its chunk.
+// Rec: the tile's record — uint4 {to, w | src_local, arg}, or uint2 without
+// the argument where every send carries the constant kArg (plan_const_arg).
+template <class Rec, uint64_t kArg = 0>
 struct TileCtx : ActorBase {
   static constexpr bool kPlain = GPA_PLAIN_CTX;
-  uint4* tile;
+  Rec* tile;
   uint32_t* cur;          // [nb] bucket cursors in the tile, two rounds per word (half sh)
   const uint32_t* st;     // [nb] bucket starts in the tile, likewise
   const uint32_t* bs;     // [nb] the bucket chunk's next free place (chunk_dst word)
@@ -1247,27 +1273,36 @@ struct TileCtx : ActorBase {
   {
     const uint32_t b = bucket_of(to);
     const uint32_t idx = (atomicAdd(&cur[b], inc) >> sh) & 0xFFFFu;
-    uint4 r;
-    r.x = to; r.y = w | src_local; r.z = (uint32_t)arg; r.w = (uint32_t)(arg >> 32);
+    Rec r;
+    r.x = to; r.y = w | src_local;
+    if constexpr(sizeof(Rec) == sizeof(uint4)) { r.z = (uint32_t)arg; r.w = (uint32_t)(arg >> 32); }
     if(idx < tcap)
       tile[idx] = r;
     else
-      xover += emit_at(r, b, bs[b], idx - ((st[b] >> sh) & 0xFFFFu), L0, nz, nxt);
+      xover += emit_at(tile_rec16(r, kArg), b, bs[b], idx - ((st[b] >> sh) & 0xFFFFu), L0, nz, nxt);
   }
 };
 
 // The two-pass paths' shared steps (the pinger's plan path, and `dp` for the
 // message-local tables). Counts per (round, bucket) come packed two rounds
-// per u32 (16-bit halves): rh[0, nb) rounds 0-1, rh[nb, 2nb) rounds 2-3.
+// per u32 (16-bit halves), NW words per bucket: dp's four drain rounds in two
+// (rh[0, nb) rounds 0-1, rh[nb, 2nb) rounds 2-3), the plan path's two
+// super-rounds in one.
 // (1) one chunk per bucket for the zone's sends: bs[b] = chunk_dst word
+template <int NW>
 __device__ __forceinline__ uint32_t plan_reserve(const uint32_t* rh, uint32_t* bs, uint32_t nb,
   uint32_t nz, uint32_t nxt, uint32_t tid)
 {
   uint32_t n_atom = 0;
   for(uint32_t b = tid; b < nb; b += kZoneThreads)
   {
-    const uint32_t w0 = rh[b], w1 = rh[nb + b];
-    const uint32_t h = (w0 & 0xFFFFu) + (w0 >> 16) + (w1 & 0xFFFFu) + (w1 >> 16);
+    uint32_t h = 0;
+#pragma unroll
+    for(int k = 0; k < NW; ++k)
+    {
+      const uint32_t w = rh[k * nb + b];
+      h += (w & 0xFFFFu) + (w >> 16);
+    }
     uint32_t base = 0;
     if(h)
     {
@@ -1284,20 +1319,30 @@ __device__ __forceinline__ uint32_t plan_reserve(const uint32_t* rh, uint32_t* b
 
 // (2) every round's bucket starts in the tile at once: exclusive scans of the
 // packed (round pair, bucket) counts, in place, each thread a contiguous run
-// of buckets; the cursors start at them. Three barriers for the four rounds
-// (a scan per round took three each). tot01 / tot23: the rounds' totals, packed.
+// of buckets; the cursors start at them. Three barriers for all the rounds
+// (a scan per round took three each). tot[k]: word k's two rounds' totals, packed.
+template <int NW>
 __device__ __forceinline__ void plan_scan(uint32_t* rh, uint32_t* cur, uint32_t nb, uint32_t* tmp2,
-  uint32_t tid, uint32_t& tot01, uint32_t& tot23)
+  uint32_t tid, uint32_t (&tot)[NW])
 {
+  static_assert(NW <= 2, "tmp2 holds two rows of wave totals");
   const uint32_t lane = tid & 63, wv = tid >> 6;
   const uint32_t per = (nb + kZoneThreads - 1) / kZoneThreads;
   const uint32_t lo = min(tid * per, nb), hi = min(lo + per, nb);
-  uint32_t a = 0, c = 0;
-  for(uint32_t b = lo; b < hi; ++b) { a += rh[b]; c += rh[nb + b]; }
-  const uint32_t ia = wave_incl_scan(a, lane), ic = wave_incl_scan(c, lane);
-  if(lane == 63) { tmp2[wv] = ia; tmp2[kZoneWaves + wv] = ic; }
+  uint32_t a[NW], ia[NW], ra[NW];
+#pragma unroll
+  for(int k = 0; k < NW; ++k) a[k] = 0;
+  for(uint32_t b = lo; b < hi; ++b)
+#pragma unroll
+    for(int k = 0; k < NW; ++k) a[k] += rh[k * nb + b];
+#pragma unroll
+  for(int k = 0; k < NW; ++k)
+  {
+    ia[k] = wave_incl_scan(a[k], lane);
+    if(lane == 63) tmp2[k * kZoneWaves + wv] = ia[k];
+  }
   lds_sync();
-  if(wv < 2)
+  if(wv < (uint32_t)NW)
   {
     uint32_t* t = tmp2 + wv * kZoneWaves;
     uint32_t x = lane < (uint32_t)kZoneWaves ? t[lane] : 0u;
@@ -1305,26 +1350,28 @@ __device__ __forceinline__ void plan_scan(uint32_t* rh, uint32_t* cur, uint32_t 
     if(lane < (uint32_t)kZoneWaves) t[lane] = x;
   }
   lds_sync();
-  uint32_t ra = (wv ? tmp2[wv - 1] : 0u) + ia - a;
-  uint32_t rc = (wv ? tmp2[kZoneWaves + wv - 1] : 0u) + ic - c;
+#pragma unroll
+  for(int k = 0; k < NW; ++k) ra[k] = (wv ? tmp2[k * kZoneWaves + wv - 1] : 0u) + ia[k] - a[k];
   for(uint32_t b = lo; b < hi; ++b)
-  {
-    const uint32_t va = rh[b], vc = rh[nb + b];
-    rh[b] = ra; cur[b] = ra; ra += va;
-    rh[nb + b] = rc; cur[nb + b] = rc; rc += vc;
-  }
-  tot01 = tmp2[kZoneWaves - 1];
-  tot23 = tmp2[2 * kZoneWaves - 1];
+#pragma unroll
+    for(int k = 0; k < NW; ++k)
+    {
+      const uint32_t v = rh[k * nb + b];
+      rh[k * nb + b] = ra[k]; cur[k * nb + b] = ra[k]; ra[k] += v;
+    }
+#pragma unroll
+  for(int k = 0; k < NW; ++k) tot[k] = tmp2[(k + 1) * kZoneWaves - 1];
   lds_sync();
 }
 
 // (3) round r's tile (m records, sorted by bucket) to the chunks: runs of one
 // chunk per wave store, every record of the thread read before the first
 // store; then each chunk's next free place for the next round (the other
-// half of bs: this round's emit still reads this one) = + the round's count
-// of the bucket, the difference of consecutive starts. Returns the records
-// the exchange lost (emit_rec).
-__device__ __forceinline__ uint32_t plan_emit(const uint4* tile, uint32_t m, const uint32_t* rst,
+// half of bs: this round's emit still reads this one; null behind the last
+// round) = + the round's count of the bucket, the difference of consecutive
+// starts. Returns the records the exchange lost (emit_rec).
+template <class Rec, uint64_t kArg = 0>
+__device__ __forceinline__ uint32_t plan_emit(const Rec* tile, uint32_t m, const uint32_t* rst,
   const uint32_t* bsr, uint32_t* bsw, uint32_t sh, uint32_t tr, uint32_t nb, uint32_t L0,
   uint32_t nz, uint32_t nxt, uint32_t tid)
 {
@@ -1332,7 +1379,7 @@ __device__ __forceinline__ uint32_t plan_emit(const uint4* tile, uint32_t m, con
   constexpr uint32_t kEU = GPA_EMIT_UNROLL;
   for(uint32_t q0 = 0; q0 < m; q0 += kEU * kZoneThreads)
   {
-    uint4 rec[kEU];
+    Rec rec[kEU];
 #pragma unroll
     for(uint32_t u = 0; u < kEU; ++u)
     {
@@ -1346,16 +1393,17 @@ __device__ __forceinline__ uint32_t plan_emit(const uint4* tile, uint32_t m, con
       if(q < m)
       {
         const uint32_t b = bucket_of(rec[u].x);
-        xover += emit_at(rec[u], b, bsr[b], q - ((rst[b] >> sh) & 0xFFFFu), L0, nz, nxt);
+        xover += emit_at(tile_rec16(rec[u], kArg), b, bsr[b], q - ((rst[b] >> sh) & 0xFFFFu), L0, nz, nxt);
       }
     }
   }
-  for(uint32_t b = tid; b < nb; b += kZoneThreads)
-  {
-    const uint32_t s0 = (rst[b] >> sh) & 0xFFFFu;
-    const uint32_t s1 = b + 1 < nb ? (rst[b + 1] >> sh) & 0xFFFFu : tr;
-    bsw[b] = bsr[b] + (s1 - s0);
-  }
+  if(bsw)
+    for(uint32_t b = tid; b < nb; b += kZoneThreads)
+    {
+      const uint32_t s0 = (rst[b] >> sh) & 0xFFFFu;
+      const uint32_t s1 = b + 1 < nb ? (rst[b + 1] >> sh) & 0xFFFFu : tr;
+      bsw[b] = bsr[b] + (s1 - s0);
+    }
   return xover;
 }
 
@@ -2014,14 +2062,20 @@ __device__ __forceinline__ bool zone_step(const uint32_t z, uint32_t cur, uint32
       // ---- 3'. order-free zone: plan, reserve, emit (no outbox) -----------------------
       constexpr int NW = HT_Words<HTS>::W;
       const TypeDev T = c_types[tz];
-      // per bucket, two rounds per u32 (16-bit halves: the zone's sends are
-      // fewer than seq_max, so no half carries into the other):
-      uint32_t* const s_rh = s_dyn;             // [2][nb] sends per (round, bucket) -> tile starts
-      uint32_t* const s_cur = s_dyn + 2 * nb;   // [2][nb] tile cursors (from the starts)
-      uint32_t* const s_bs = s_dyn + 4 * nb;    // [2][nb] each chunk's next free place (chunk_dst),
-                                                //   round r reads half r & 1, writes the other
-      uint4* const tile = s_pool;                // pass 2 (the whole pool)
-      for(uint32_t b = tid; b < 2 * nb; b += kZoneThreads) s_rh[b] = 0;
+      // Pass 2 runs in two super-rounds of kPerSuper drain rounds each (two
+      // actors per thread): the tile's records are 8 bytes, so the pool
+      // holds a super-round's sends, and the barrier pairs, the emits and
+      // the updates of the chunks' next free places are two, not four.
+      // per bucket, one u32 with both super-rounds' counts (16-bit halves:
+      // the zone's sends are fewer than seq_max, so no half carries into
+      // the other):
+      constexpr uint64_t kArg = plan_const_arg<HTS>();
+      uint32_t* const s_rh = s_dyn;             // [nb] sends per (super-round, bucket) -> tile starts
+      uint32_t* const s_cur = s_dyn + nb;       // [nb] tile cursors (from the starts)
+      uint32_t* const s_bs = s_dyn + 2 * nb;    // [2][nb] each chunk's next free place (chunk_dst),
+                                                //   super-round q reads half q, writes the other
+      uint2* const tile = reinterpret_cast<uint2*>(s_pool);     // pass 2 (the whole pool)
+      for(uint32_t b = tid; b < nb; b += kZoneThreads) s_rh[b] = 0;
       // Lanes of a wave run their actors' behaviours side by side, so a wave
       // takes as long as its busiest lane, and the four waves a SIMD holds
       // share its VALU. The zone's actors are therefore dealt to threads by
@@ -2030,7 +2084,14 @@ __device__ __forceinline__ bool zone_step(const uint32_t z, uint32_t cur, uint32
       // block (wave w, round r) = 8g + (r or 7 - r) for j = w (or W - 1 - w
       // on odd rounds), g = j / 2 — every wave gets alike counts in its lanes
       // and a like total over its rounds, and every round a like share of
-      // the zone's sends (the tile). The state moves through LDS (coalesced
+      // the zone's sends (the tile). Rounds 2q and 2q + 1 make super-round
+      // q: a wave's blocks there are 8g + {0, 2}[q] and 8g' + {6, 4}[q] (j
+      // even; g' = W / 2 - 1 - g), or 8g + {7, 5}[q] and 8g' + {1, 3}[q] (j
+      // odd) — the block numbers, which stand for the counts, sum to
+      // 8 (g + g') + 6 (or + 8) in either super-round, so a wave's two
+      // super-rounds carry like totals, and of every eight blocks
+      // super-round 0 takes {0, 1, 6, 7}, super-round 1 {2, 3, 4, 5}: like
+      // shares of the zone's sends. The state moves through LDS (coalesced
       // loads — issued before the count phase — and stores; the permuted
       // threads read and write it there).
       constexpr bool kStageApart =
@@ -2089,8 +2150,8 @@ __device__ __forceinline__ bool zone_step(const uint32_t z, uint32_t cur, uint32
         pc.self = (L0 + i) * R + me;
         pc.src_local = i;
         pc.type = tz;
-        pc.rh = s_rh + (r >> 1) * nb;
-        pc.inc = (r & 1u) ? 0x10000u : 1u;
+        pc.rh = s_rh;
+        pc.inc = (r / kPerSuper) ? 0x10000u : 1u;
         uint64_t sc[NW];
 #pragma unroll
         for(int k = 0; k < NW; ++k) sc[k] = st[r][k];
@@ -2099,19 +2160,19 @@ __device__ __forceinline__ bool zone_step(const uint32_t z, uint32_t cur, uint32
       lds_sync();
       GPA_STAMP(3);
       // one chunk per bucket for the zone's sends
-      n_atom += plan_reserve(s_rh, s_bs, nb, nz, nxt, tid);
+      n_atom += plan_reserve<1>(s_rh, s_bs, nb, nz, nxt, tid);
       GPA_STAMP(5);
 #ifdef GPA_STAMPS
       const unsigned long long t_scan = __builtin_amdgcn_s_memtime();
 #endif
-      // every round's bucket starts in the tile at once
-      uint32_t tot01, tot23;
-      plan_scan(s_rh, s_cur, nb, s_tmp2, tid, tot01, tot23);
+      // both super-rounds' bucket starts in the tile at once
+      uint32_t tot[1];
+      plan_scan<1>(s_rh, s_cur, nb, s_tmp2, tid, tot);
 #ifdef GPA_STAMPS
       GPA_ACC(9, t_scan);
 #endif
-      // pass 2, one round at a time
-      TileCtx tc;
+      // pass 2, one super-round at a time
+      TileCtx<uint2, kArg> tc;
       tc.reset_common();
       tc.tile = tile;
       tc.tcap = kPlanTile;
@@ -2120,47 +2181,50 @@ __device__ __forceinline__ bool zone_step(const uint32_t z, uint32_t cur, uint32
 #ifdef GPA_STAMPS
       unsigned long long emit_clk = 0, t_emit = 0;    // diagnostic build: Σ tile-emit time
 #endif
+      tc.cur = s_cur;
+      tc.st = s_rh;
+      tc.type = tz;
 #pragma unroll
-      for(uint32_t r = 0; r < kRounds; ++r)
+      for(uint32_t q = 0; q < kSuper; ++q)
       {
-        const uint32_t sh = (r & 1u) * 16u;
-        const uint32_t* const rst = s_rh + (r >> 1) * nb;       // the round's starts (half sh)
-        const uint32_t tr = (((r >> 1) ? tot23 : tot01) >> sh) & 0xFFFFu;   // the round's sends
-        tc.cur = s_cur + (r >> 1) * nb;
-        const uint32_t* const bsr = s_bs + (r & 1u) * nb;
-        uint32_t* const bsw = s_bs + ((r & 1u) ^ 1u) * nb;
-        tc.st = rst; tc.bs = bsr;
+        const uint32_t sh = q * 16u;                            // the super-round's half
+        const uint32_t tr = (tot[0] >> sh) & 0xFFFFu;           // its sends
+        const uint32_t* const bsr = s_bs + q * nb;
+        uint32_t* const bsw = q + 1 < kSuper ? s_bs + (q ^ 1u) * nb : nullptr;
+        tc.bs = bsr;
         tc.sh = sh; tc.inc = 1u << sh;
 #ifdef GPA_STAMPS
         const unsigned long long t_hand = __builtin_amdgcn_s_memtime();
 #endif
-        if(nm[r])
-        {
-          const uint32_t i = ai[r];
-          const uint32_t L = L0 + i;
-          tc.li = L - T.lfirst;
-          tc.self = L * R + me;
-          tc.src_local = i;
-          tc.type = tz;
-          tc.seq = 0;
-          for(uint32_t j = 0; j < nm[r]; ++j) handle(HtTag<HTS>{}, T, tc, st[r], 0u, 0ull);
-          // overloaded iff a full batch ran (batch_limit_reached, actor.c:369-381);
-          // nothing here mutes
-          const bool full = T.prio ? (nm[r] % T.batch == 0u) : nm[r] == T.batch;
-          s_tb[i] = full ? 1u : 0u;
-          if(full) atomicAdd(&s_ntrig, 1u);
-          delivered += nm[r];
-          active += 1;
-          dz += nm[r];
-        }
+#pragma unroll
+        for(uint32_t r = q * kPerSuper; r < (q + 1) * kPerSuper; ++r)
+          if(nm[r])
+          {
+            const uint32_t i = ai[r];
+            const uint32_t L = L0 + i;
+            tc.li = L - T.lfirst;
+            tc.self = L * R + me;
+            tc.src_local = i;
+            tc.seq = 0;
+            for(uint32_t j = 0; j < nm[r]; ++j) handle(HtTag<HTS>{}, T, tc, st[r], 0u, 0ull);
+            // overloaded iff a full batch ran (batch_limit_reached, actor.c:369-381);
+            // nothing here mutes
+            const bool full = T.prio ? (nm[r] % T.batch == 0u) : nm[r] == T.batch;
+            s_tb[i] = full ? 1u : 0u;
+            if(full) atomicAdd(&s_ntrig, 1u);
+            delivered += nm[r];
+            active += 1;
+            dz += nm[r];
+          }
         lds_sync();
 #ifdef GPA_STAMPS
         GPA_ACC(10, t_hand);
         t_emit = __builtin_amdgcn_s_memtime();
 #endif
         // the tile, sorted by bucket, to the chunks; the chunks' next free
-        // places for the next round
-        xover += plan_emit(tile, min(tr, kPlanTile), rst, bsr, bsw, sh, tr, nb, L0, nz, nxt, tid);
+        // places for the next super-round
+        xover += plan_emit<uint2, kArg>(tile, min(tr, kPlanTile), s_rh, bsr, bsw, sh, tr, nb, L0, nz,
+                                        nxt, tid);
         lds_sync();
 #ifdef GPA_STAMPS
         emit_clk += __builtin_amdgcn_s_memtime() - t_emit;
@@ -2239,9 +2303,9 @@ __device__ __forceinline__ bool zone_step(const uint32_t z, uint32_t cur, uint32
       uint32_t* const s_rh = s_dyn;             // [2][nb] sends per (round, bucket) -> tile starts
       uint32_t* const s_cur = s_dyn + 2 * nb;   // [2][nb] tile cursors
       uint32_t* const s_bs = s_dyn + 4 * nb;    // [2][nb] chunks' next free places (ping-pong)
-      n_atom += plan_reserve(s_rh, s_bs, nb, nz, nxt, tid);
-      uint32_t tot01, tot23;
-      plan_scan(s_rh, s_cur, nb, s_tmp2, tid, tot01, tot23);
+      n_atom += plan_reserve<2>(s_rh, s_bs, nb, nz, nxt, tid);
+      uint32_t tot[2];
+      plan_scan<2>(s_rh, s_cur, nb, s_tmp2, tid, tot);
       // each thread's actors (one a round) in registers: the per-actor arrays'
       // part of the pool becomes the tile, up to the index at its end
       // (packed: segment offset << 8 | count; plain zones' counts are at
@@ -2260,7 +2324,7 @@ __device__ __forceinline__ bool zone_step(const uint32_t z, uint32_t cur, uint32
       if(tid == 0) { c_eng.dbg[z * kDbgSlots + 9] = 0; c_eng.dbg[z * kDbgSlots + 10] = 0; }
 #endif
       const uint16_t* const s_ix = dp_index(s_pool, nl);
-      TileCtx tc;
+      TileCtx<uint4> tc;
       tc.reset_common();
       tc.tile = s_pool;
       tc.tcap = dp_tile_cap(nl);
@@ -2272,10 +2336,10 @@ __device__ __forceinline__ bool zone_step(const uint32_t z, uint32_t cur, uint32
       {
         const uint32_t sh = (r & 1u) * 16u;
         const uint32_t* const rst = s_rh + (r >> 1) * nb;
-        const uint32_t tr = (((r >> 1) ? tot23 : tot01) >> sh) & 0xFFFFu;
+        const uint32_t tr = (tot[r >> 1] >> sh) & 0xFFFFu;
         tc.cur = s_cur + (r >> 1) * nb;
         const uint32_t* const bsr = s_bs + (r & 1u) * nb;
-        uint32_t* const bsw = s_bs + ((r & 1u) ^ 1u) * nb;
+        uint32_t* const bsw = r + 1 < kRounds ? s_bs + ((r & 1u) ^ 1u) * nb : nullptr;
         tc.st = rst; tc.bs = bsr;
         tc.sh = sh; tc.inc = 1u << sh;
 #ifdef GPA_STAMPS
@@ -2305,7 +2369,7 @@ __device__ __forceinline__ bool zone_step(const uint32_t z, uint32_t cur, uint32
         GPA_ACC(9, t_dr);                     // the round's drain (to its barrier)
         const unsigned long long t_em = __builtin_amdgcn_s_memtime();
 #endif
-        xover += plan_emit(s_pool, min(tr, tc.tcap), rst, bsr, bsw, sh, tr, nb, L0, nz, nxt, tid);
+        xover += plan_emit<uint4>(s_pool, min(tr, tc.tcap), rst, bsr, bsw, sh, tr, nb, L0, nz, nxt, tid);
         lds_sync();
 #ifdef GPA_STAMPS
         GPA_ACC(10, t_em);                    // the round's tile emit
@@ -2755,6 +2819,7 @@ __device__ __forceinline__ bool zone_step(const uint32_t z, uint32_t cur, uint32
                   : tid == 3 ? ST_DROPPED : tid == 4 ? ST_XCHG_OVERFLOW : ST_ATOMICS;
     if(tot) stat_add_z(idx, z, tot);
   }
+  if(plan && tid == 6) stat_add_z(ST_PLAN_ZONES, z, 1ull);
   if(took_mail && tid == 0)
   {
     if(nc + nl) pend_add_z(pend_slot, z, (unsigned long long)(nc + nl));
