@@ -23,6 +23,7 @@
 #include <thread>
 #include <vector>
 
+#include "../../include/gpu_actor_host.h"
 #include "engine_dev.h"
 #include "zone_dev.h"
 #include "sparse_dev.h"
@@ -182,6 +183,58 @@ __global__ void k_spawn_commit(const uint32_t* tcnt, unsigned long long* live)
   if(t >= GPU_ACTOR_MAX_TYPES || tcnt[t] == 0) return;
   const unsigned long long room = c_types[t].count - live[t];
   live[t] += tcnt[t] < room ? tcnt[t] : room;
+}
+
+// ---- messages to the host (include/gpu_actor_host.h; engine_dev.h send_host) --
+// Before every step of an engine with port types: the step's index since the
+// last collection, shifted above the key's sender bits (EngDev::host_step).
+__global__ void k_host_begin(uint64_t* step_word, uint64_t v)
+{
+  *step_word = v;
+}
+
+// The listed messages of the kHostShards segments as one run: off[s] is where
+// segment s's records start in it (the host read the segments' counts); the
+// run's keys, and for each its place in the list, go to the sort.
+struct HostOff { uint32_t off[kHostShards + 1]; };
+__global__ void __launch_bounds__(kBlock) k_host_compact(const uint64_t* key, HostOff o, uint32_t seg,
+  uint64_t* key_out, uint32_t* idx_out)
+{
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if(i >= o.off[kHostShards]) return;
+  uint32_t lo = 0, hi = kHostShards - 1;         // last segment with off <= i
+  while(lo < hi)
+  {
+    const uint32_t mid = (lo + hi + 1) / 2;
+    if(o.off[mid] <= i) lo = mid; else hi = mid - 1;
+  }
+  const uint32_t at = lo * seg + (i - o.off[lo]);  // < kHostShards * seg: i - off[lo] < the segment's count <= seg
+  key_out[i] = key[at];
+  idx_out[i] = at;
+}
+
+// The first n records in key order as gpu_host_msg_t (32 B: two 16-byte
+// stores a lane, consecutive lanes consecutive records): key = step since
+// `base` << kshift | from << 16 | seq, idx the record's place in the list.
+__global__ void __launch_bounds__(kBlock) k_host_gather(const uint64_t* key, const uint32_t* idx,
+  const uint4* rec, gpu_host_msg_t* out, uint32_t n, uint64_t base, uint32_t kshift)
+{
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if(i >= n) return;
+  const uint64_t k = key[i];
+  const uint4 r = rec[idx[i]];
+  const uint64_t step = base + (k >> kshift);
+  const uint32_t from = (uint32_t)((k & ((1ull << kshift) - 1ull)) >> 16);
+  uint4* o = reinterpret_cast<uint4*>(out + i);
+  o[0] = make_uint4((uint32_t)step, (uint32_t)(step >> 32), from, (uint32_t)(k & 0xFFFFull));
+  o[1] = r;                                        // to, behaviour, arg
+}
+static_assert(sizeof(gpu_host_msg_t) == 32, "gpu_host_msg_t is 32 B");
+
+// messages a collection held more of than the reserve (gpu_actor_host_reserve)
+__global__ void k_host_lost(unsigned long long n)
+{
+  c_eng.stats[ST_DROPPED] += n;
 }
 
 // ---- records past a zone's capacity (SpillRec, engine_dev.h) ----------------
@@ -453,6 +506,32 @@ struct Engine {
   // zone geometry: actors per zone = 1 << zbits (step_entry.h; chosen by
   // relayout_zones)
   uint32_t zbits = kZoneBits;
+  // messages to the host (include/gpu_actor_host.h): host_ports once a port
+  // type exists (nothing below is allocated, launched or waited for before);
+  // host_dirty: steps ran since the last collection, the first of them step
+  // host_base; host_defer: gpu_actor_run_fixed is launching (it collects
+  // nothing itself). The list (EngDev::host_*: kHostShards segments of
+  // host_seg records), the compacted and the sorted keys and places, the
+  // gathered messages and their pinned mirror; the key's step field starts
+  // at bit host_kshift (16 sequence bits + the bits of max_actors - 1).
+  bool host_ports = false, host_dirty = false, host_defer = false;
+  uint32_t host_base = 0;
+  uint64_t host_reserve = GPU_ACTOR_HOST_RESERVE_DEFAULT;
+  uint32_t host_seg = 0, host_kshift = 48;
+  uint64_t *d_host_key = nullptr, *d_host_kc = nullptr, *d_host_ks = nullptr;
+  uint32_t *d_host_ic = nullptr, *d_host_is = nullptr;
+  uint4* d_host_rec = nullptr;
+  unsigned int* d_host_n = nullptr;
+  unsigned int* h_host_n = nullptr;        // pinned
+  uint64_t* d_host_step = nullptr;
+  gpu_host_msg_t* d_host_out = nullptr;
+  gpu_host_msg_t* h_host_out = nullptr;    // pinned
+  // collected messages not yet received (gpu_actor_recv), from hostq_head on;
+  // or the callback that takes them instead (gpu_actor_host_notify)
+  std::vector<gpu_host_msg_t> hostq;
+  size_t hostq_head = 0;
+  gpu_actor_host_fn host_fn = nullptr;
+  void* host_ctx = nullptr;
 };
 
 Engine g;
@@ -492,9 +571,13 @@ inline uint32_t blocks_for(uint64_t n, uint32_t bs = kBlock) { return (uint32_t)
 // actors per zone in this engine's geometry
 inline uint32_t zone_actors() { return 1u << g.zbits; }
 
+// tables whose actors are no serial actors: they have no mailbox and never
+// run, take no zone capacity, and do not count towards the step kernel's
+// choice — the reducible types, and host ports (include/gpu_actor_host.h)
 inline bool reducible_ht(uint32_t ht)
 {
-  return ht == GPU_ACTOR_HT_FANIN_ANALYZER || ht == GPU_ACTOR_HT_GUPS_UPDATER;
+  return ht == GPU_ACTOR_HT_FANIN_ANALYZER || ht == GPU_ACTOR_HT_GUPS_UPDATER ||
+         ht == GPU_ACTOR_HT_HOST_PORT;
 }
 
 const std::vector<StepEntry>& step_entries()
@@ -756,6 +839,26 @@ int upload_types()
     g.fuse = !(fu && atoi(fu) == 0);
   }
   e.zplan = g.d_zplan;
+  if(g.host_ports && g.host_seg)     // (host_seg 0: the lists could not be allocated)
+  {
+    uint64_t lo = ~0ull, hi = 0;
+    for(uint32_t t = 0; t < GPU_ACTOR_MAX_TYPES; ++t)
+    {
+      const HostType& h = g.types[t];
+      if(!h.created || h.ht != GPU_ACTOR_HT_HOST_PORT) continue;
+      e.host_rng[e.host_nrng].first = (uint32_t)h.first;
+      e.host_rng[e.host_nrng].count = (uint32_t)h.count;
+      e.host_rng[e.host_nrng].type = t;
+      e.host_nrng++;
+      lo = std::min(lo, h.first);
+      hi = std::max(hi, h.first + h.count);
+    }
+    e.host_first = e.host_nrng ? (uint32_t)lo : 0u;
+    e.host_span = e.host_nrng ? (uint32_t)(hi - lo) : 0u;
+    e.host_seg = g.host_seg;
+    e.host_key = g.d_host_key; e.host_rec = g.d_host_rec; e.host_n = g.d_host_n;
+    e.host_step = g.d_host_step;
+  }
   {
     const int rc = gups_setup(e);
     if(rc) return rc;
@@ -1081,6 +1184,7 @@ uint32_t required_words(uint32_t ht)
     case GPU_ACTOR_HT_FIFO_SINK: return 11;
     case GPU_ACTOR_HT_SPREADER: return 5;
     case GPU_ACTOR_HT_PROGRAM: return 8;
+    case GPU_ACTOR_HT_HOST_PORT: return 1;
     default: return 0;
   }
 }
@@ -2083,6 +2187,139 @@ int spawn_process(uint32_t cur)
   return 0;
 }
 
+// ---- messages to the host (include/gpu_actor_host.h) -------------------------
+// Device room for g.host_reserve messages: kHostShards segments whose sizes
+// sum to at least the reserve (send_host fills a full segment's neighbours, so
+// nothing is lost before every segment is full; a collection keeps at most
+// the reserve). Called with nothing listed (between collections).
+void host_free()
+{
+  if(g.d_host_key) (void)hipFree(g.d_host_key);
+  if(g.d_host_kc) (void)hipFree(g.d_host_kc);
+  if(g.d_host_ks) (void)hipFree(g.d_host_ks);
+  if(g.d_host_ic) (void)hipFree(g.d_host_ic);
+  if(g.d_host_is) (void)hipFree(g.d_host_is);
+  if(g.d_host_rec) (void)hipFree(g.d_host_rec);
+  if(g.d_host_out) (void)hipFree(g.d_host_out);
+  if(g.h_host_out) (void)hipHostFree(g.h_host_out);
+  g.d_host_key = g.d_host_kc = g.d_host_ks = nullptr;
+  g.d_host_ic = g.d_host_is = nullptr;
+  g.d_host_rec = nullptr; g.d_host_out = nullptr; g.h_host_out = nullptr;
+  g.host_seg = 0;
+}
+
+int host_alloc()
+{
+  HIPCK(hipStreamSynchronize(g.stream));        // no step still lists into the old segments
+  host_free();
+  if(!g.d_host_n)
+  {
+    HIPCK(hipMalloc(&g.d_host_n, kHostShards * sizeof(unsigned int)));
+    HIPCK(hipMemsetAsync(g.d_host_n, 0, kHostShards * sizeof(unsigned int), g.stream));
+    HIPCK(hipHostMalloc(&g.h_host_n, kHostShards * sizeof(unsigned int), hipHostMallocDefault));
+    HIPCK(hipMalloc(&g.d_host_step, sizeof(uint64_t)));
+    HIPCK(hipMemsetAsync(g.d_host_step, 0, sizeof(uint64_t), g.stream));
+  }
+  const uint64_t n = g.host_reserve;
+  const uint32_t seg = (uint32_t)((n + kHostShards - 1) / kHostShards);
+  const size_t room = (size_t)seg * kHostShards;
+  auto ck = [](hipError_t e) { if(e != hipSuccess) (void)hipGetLastError(); return e == hipSuccess; };
+  if(!ck(hipMalloc(&g.d_host_key, room * sizeof(uint64_t))) ||
+     !ck(hipMalloc(&g.d_host_kc, room * sizeof(uint64_t))) ||
+     !ck(hipMalloc(&g.d_host_ks, room * sizeof(uint64_t))) ||
+     !ck(hipMalloc(&g.d_host_ic, room * sizeof(uint32_t))) ||
+     !ck(hipMalloc(&g.d_host_is, room * sizeof(uint32_t))) ||
+     !ck(hipMalloc(&g.d_host_rec, room * sizeof(uint4))) ||
+     !ck(hipMalloc(&g.d_host_out, n * sizeof(gpu_host_msg_t))) ||
+     !ck(hipHostMalloc(&g.h_host_out, n * sizeof(gpu_host_msg_t), hipHostMallocDefault)))
+  {
+    host_free();
+    return GPU_ACTOR_ENOMEM;
+  }
+  g.host_seg = seg;
+  // the key: 16 sequence bits, the bits of an id below max_actors, the step
+  // since the last collection above them
+  uint32_t fbits = 1;
+  while(fbits < 32 && (1ull << fbits) < g.cfg.max_actors) ++fbits;
+  g.host_kshift = 16 + fbits;
+  return 0;
+}
+
+// steps one collection's keys can tell apart (gpu_actor_run_fixed checks)
+inline uint64_t host_step_room()
+{
+  return std::min<uint64_t>(1ull << (64 - g.host_kshift), 1ull << 31);
+}
+
+// The messages listed since the last collection, made canonical and handed to
+// the host: one readback of the segments' counts (the wait that engines with
+// spawning types make in spawn_process); then, when there are any, the
+// segments compacted to one run, sorted by key (step, sender, sequence),
+// gathered as gpu_host_msg_t, copied out in one piece, and the counts cleared
+// on the stream. They go to the notify callback, or the queue gpu_actor_recv
+// empties. A collection that holds more than the reserve keeps the first
+// `reserve` in key order; the rest count as dropped.
+int host_collect()
+{
+  if(!g.host_dirty) return 0;
+  HIPCK(hipMemcpyAsync(g.h_host_n, g.d_host_n, kHostShards * sizeof(unsigned int),
+    hipMemcpyDeviceToHost, g.stream));
+  HIPCK(hipStreamSynchronize(g.stream));
+  const uint32_t steps = g.sidx - g.host_base;
+  g.host_dirty = false;
+  HostOff o;
+  uint64_t total = 0;
+  for(uint32_t s = 0; s < kHostShards; ++s)
+  {
+    o.off[s] = (uint32_t)total;
+    total += std::min<unsigned int>(g.h_host_n[s], g.host_seg);
+  }
+  o.off[kHostShards] = (uint32_t)total;
+  if(total == 0) return 0;
+  const uint32_t n = (uint32_t)total;
+  hipLaunchKernelGGL(k_host_compact, dim3(blocks_for(n)), dim3(kBlock), 0, g.stream,
+    (const uint64_t*)g.d_host_key, o, g.host_seg, g.d_host_kc, g.d_host_ic);
+  HIPCK(hipGetLastError());
+  int end_bit = (int)g.host_kshift;
+  while(end_bit < 64 && (uint64_t)steps > (1ull << (end_bit - (int)g.host_kshift))) ++end_bit;
+  size_t need = 0;
+  HIPCK(hipcub::DeviceRadixSort::SortPairs(nullptr, need, g.d_host_kc, g.d_host_ks, g.d_host_ic,
+    g.d_host_is, (int)n, 0, end_bit, g.stream));
+  if(need > g.sort_tmp_bytes)
+  {
+    if(g.d_sort_tmp) HIPCK(hipFree(g.d_sort_tmp));
+    g.d_sort_tmp = nullptr;
+    g.sort_tmp_bytes = 0;
+    HIPCK(hipMalloc(&g.d_sort_tmp, need));
+    g.sort_tmp_bytes = need;
+  }
+  HIPCK(hipcub::DeviceRadixSort::SortPairs(g.d_sort_tmp, need, g.d_host_kc, g.d_host_ks, g.d_host_ic,
+    g.d_host_is, (int)n, 0, end_bit, g.stream));
+  const uint32_t keep = (uint32_t)std::min<uint64_t>(n, g.host_reserve);
+  hipLaunchKernelGGL(k_host_gather, dim3(blocks_for(keep)), dim3(kBlock), 0, g.stream,
+    (const uint64_t*)g.d_host_ks, (const uint32_t*)g.d_host_is, (const uint4*)g.d_host_rec,
+    g.d_host_out, keep, (uint64_t)g.host_base, g.host_kshift);
+  if(n > keep)
+  {
+    hipLaunchKernelGGL(k_host_lost, dim3(1), dim3(1), 0, g.stream, (unsigned long long)(n - keep));
+    g.dev_epoch++;
+  }
+  HIPCK(hipGetLastError());
+  HIPCK(hipMemcpyAsync(g.h_host_out, g.d_host_out, (size_t)keep * sizeof(gpu_host_msg_t),
+    hipMemcpyDeviceToHost, g.stream));
+  HIPCK(hipMemsetAsync(g.d_host_n, 0, kHostShards * sizeof(unsigned int), g.stream));
+  HIPCK(hipStreamSynchronize(g.stream));
+  if(g.host_fn)
+    g.host_fn(g.host_ctx, g.h_host_out, keep);
+  else
+  {
+    if(g.hostq_head == g.hostq.size()) { g.hostq.clear(); g.hostq_head = 0; }
+    try { g.hostq.insert(g.hostq.end(), g.h_host_out, g.h_host_out + keep); }
+    catch(...) { return GPU_ACTOR_ENOMEM; }
+  }
+  return 0;
+}
+
 // One superstep: k_step on parity g.par (+ exchange), then flip parity.
 // The run-time compiled step this engine's tables take (jit_host.h), built
 // or loaded once per set (a set whose build fails stays on the compiled-in
@@ -2167,6 +2404,17 @@ int launch_step(uint32_t slot, hipEvent_t e0, hipEvent_t e1)
   const uint64_t nb = g.n_zones + (R() > 1 ? R() : 0);
   if(!step_fits(se, nb)) return GPU_ACTOR_ERANGE;    // more buckets than a workgroup's LDS holds
   const size_t dyn = step_dyn_bytes(se, nb);
+  // an engine with host ports: this step's place in the keys of the messages
+  // it sends out (send_host reads it), counted from the first step since the
+  // last collection
+  if(g.host_ports)
+  {
+    if(!g.host_seg) return GPU_ACTOR_ENOMEM;     // a failed gpu_actor_host_reserve left no lists
+    if(!g.host_dirty) { g.host_base = g.sidx; g.host_dirty = true; }
+    hipLaunchKernelGGL(k_host_begin, dim3(1), dim3(1), 0, g.stream, g.d_host_step,
+      (uint64_t)(g.sidx - g.host_base) << g.host_kshift);
+    HIPCK(hipGetLastError());
+  }
   // the run-time compiled step (jit_ensure), when it builds and fits: the
   // programs' as two launches like the interpreter's, or a mix's one launch
   // with k_hot before it where hot zones are prepared
@@ -2346,6 +2594,13 @@ int step_after_launch(uint32_t slot, hipEvent_t e0, hipEvent_t e1)
     int rc = spawn_process(g.par);
     if(rc) return rc;
   }
+  // the messages this step sent to host ports (gpu_actor_run_fixed leaves
+  // them to the next call that observes the engine)
+  if(g.host_ports && !g.host_defer)
+  {
+    int rc = host_collect();
+    if(rc) return rc;
+  }
   return 0;
 }
 
@@ -2485,6 +2740,16 @@ void free_all()
   if(g.d_spill_flag) (void)hipFree(g.d_spill_flag);
   if(g.h_sbuf) (void)hipHostFree(g.h_sbuf);
   if(g.h_rbuf) (void)hipHostFree(g.h_rbuf);
+  host_free();
+  if(g.d_host_n) (void)hipFree(g.d_host_n);
+  if(g.h_host_n) (void)hipHostFree(g.h_host_n);
+  if(g.d_host_step) (void)hipFree(g.d_host_step);
+  g.d_host_n = nullptr; g.h_host_n = nullptr; g.d_host_step = nullptr;
+  g.host_ports = g.host_dirty = g.host_defer = false;
+  g.host_base = 0;
+  g.host_reserve = GPU_ACTOR_HOST_RESERVE_DEFAULT;
+  g.hostq.clear(); g.hostq_head = 0;
+  g.host_fn = nullptr; g.host_ctx = nullptr;
   for(hipEvent_t e : g.ev) (void)hipEventDestroy(e);
   if(g.comm) (void)ncclCommDestroy(g.comm);
   if(g.stream) (void)hipStreamDestroy(g.stream);
@@ -2494,6 +2759,11 @@ void free_all()
 // share; k_inject lands only local mail).
 inline bool host_msg_ok(const gpu_msg_t& m)
 {
+  // (a host port has no mailbox: only programs address it, gpu_actor_host.h)
+  // (the ranges upload_types worked out: one test for every other target)
+  if(m.to - g.eng_host.host_first < g.eng_host.host_span)
+    for(uint32_t k = 0; k < g.eng_host.host_nrng; ++k)
+      if(m.to - g.eng_host.host_rng[k].first < g.eng_host.host_rng[k].count) return false;
   return m.to < g.n_actors && m.behaviour <= 0xF && (R() == 1 || m.to % R() == rank());
 }
 
@@ -2540,6 +2810,15 @@ int sendv_locked(const gpu_msg_t* first, uint64_t n)
   int rc = flush_sends();                   // earlier single sends go first
   if(rc) return rc;
   return inject_locked(first, n);
+}
+
+// Ahead of a call that observes the engine: staged host sends go in, and the
+// messages to host ports a gpu_actor_run_fixed left listed on the device come
+// out (nothing to do, and no wait, in an engine without ports).
+int observe()
+{
+  const int rc = flush_sends();
+  return rc ? rc : host_collect();
 }
 
 } // namespace
@@ -2920,6 +3199,14 @@ GPU_ACTOR_API int gpu_actor_create(uint32_t type_id, uint64_t count, uint64_t* f
   const uint64_t lo = owned_below(g.n_actors), hi = owned_below(g.n_actors + count);
   const uint32_t n_local = (uint32_t)hi;
   if((n_local + kZone - 1) / kZone > kMaxZones) return GPU_ACTOR_ERANGE;
+  if(t.ht == GPU_ACTOR_HT_HOST_PORT && !g.host_ports)
+  {
+    // the first port type: room for the messages programs send out (before
+    // anything of the type exists: a failure leaves it uncreated)
+    const int hrc = host_alloc();
+    if(hrc) return hrc;
+    g.host_ports = true;
+  }
   t.first = g.n_actors;
   t.count = count;
   t.lfirst = (uint32_t)lo;
@@ -3034,7 +3321,8 @@ GPU_ACTOR_API int gpu_actor_send(uint64_t to, uint32_t behaviour, uint64_t arg)
 bool sparse_ok()
 {
   const char* e = getenv("GPA_NO_SPARSE");
-  return !(e && atoi(e) != 0) && R() == 1 && g.spawn_cap == 0 && g.n_zones > 0;
+  // (nor with host ports: their messages are keyed and collected per k_step)
+  return !(e && atoi(e) != 0) && R() == 1 && g.spawn_cap == 0 && g.n_zones > 0 && !g.host_ports;
 }
 
 // One k_sparse launch from parity g.par: up to max_steps supersteps (0: no
@@ -3122,7 +3410,7 @@ int run_locked(uint64_t max_steps, uint64_t* steps_done)
 {
   if(!g.init) return GPU_ACTOR_ESTATE;
   {
-    const int frc = flush_sends();
+    const int frc = observe();
     if(frc) return frc;
   }
   uint64_t done = 0;
@@ -3306,6 +3594,24 @@ GPU_ACTOR_API int gpu_actor_run_fixed(uint64_t n)
   if(rc) return rc;
   rc = settle_spills();
   if(rc) return rc;
+  // host ports: these steps' messages stay listed on the device until the
+  // next call that observes the engine (no wait is added here); their keys
+  // tell host_step_room() steps apart, so a list that would span more is
+  // collected first
+  struct HostDefer {
+    HostDefer() { g.host_defer = true; }
+    ~HostDefer() { g.host_defer = false; }
+  };
+  if(g.host_ports)
+  {
+    if(n > host_step_room()) return GPU_ACTOR_ERANGE;
+    if(g.host_dirty && (uint64_t)(g.sidx - g.host_base) + n > host_step_room())
+    {
+      rc = host_collect();
+      if(rc) return rc;
+    }
+  }
+  HostDefer defer;
   uint64_t left = n;
   double ms_total = 0.0;
   while(left)
@@ -3380,7 +3686,7 @@ GPU_ACTOR_API int gpu_actor_sync(void)
   std::lock_guard<std::mutex> lk(g.mu);
   if(!g.init) return GPU_ACTOR_ESTATE;
   {
-    const int frc = flush_sends();
+    const int frc = observe();
     if(frc) return frc;
   }
   HIPCK(hipStreamSynchronize(g.stream));
@@ -3393,7 +3699,7 @@ GPU_ACTOR_API int gpu_actor_state_read(uint32_t type_id, uint64_t first, uint64_
   std::lock_guard<std::mutex> lk(g.mu);
   if(!g.init) return GPU_ACTOR_ESTATE;
   {
-    const int frc = flush_sends();
+    const int frc = observe();
     if(frc) return frc;
   }
   if(type_id >= GPU_ACTOR_MAX_TYPES || !out) return GPU_ACTOR_EINVAL;
@@ -3441,7 +3747,7 @@ GPU_ACTOR_API int gpu_actor_counts(gpu_actor_counts_t* out)
   std::lock_guard<std::mutex> lk(g.mu);
   if(!g.init) return GPU_ACTOR_ESTATE;
   {
-    const int frc = flush_sends();
+    const int frc = observe();
     if(frc) return frc;
   }
   if(!out) return GPU_ACTOR_EINVAL;
@@ -3493,6 +3799,79 @@ GPU_ACTOR_API uint32_t gpu_actor_owner(uint64_t id)
 GPU_ACTOR_API void* gpu_actor_stream(void) { return (void*)g.stream; }
 
 GPU_ACTOR_API double gpu_actor_last_drain_ms(void) { return g.last_drain_ms; }
+
+// ---- messages to the host (include/gpu_actor_host.h) -------------------------
+GPU_ACTOR_API int gpu_actor_host_reserve(uint64_t n)
+{
+  if(g.async_busy) return GPU_ACTOR_EBUSY;
+  std::lock_guard<std::mutex> lk(g.mu);
+  if(!g.init) return GPU_ACTOR_ESTATE;
+  if(g.async_busy) return GPU_ACTOR_EBUSY;
+  // (the segments' room, reserve rounded up to kHostShards, is sorted with an int count)
+  if(n == 0 || n > (1ull << 30)) return GPU_ACTOR_EINVAL;
+  if(n == g.host_reserve && (!g.host_ports || g.host_seg)) return 0;
+  int rc = observe();                       // what the old room still holds
+  if(rc) return rc;
+  const uint64_t old = g.host_reserve;
+  g.host_reserve = n;
+  if(!g.host_ports) return 0;               // allocated with the first port type
+  rc = host_alloc();
+  if(rc)
+  {
+    g.host_reserve = old;
+    if(host_alloc() != 0)
+    {
+      // no room at either size: the device constants must not keep the freed
+      // lists (uploaded without ports: span 0), and no step runs until a
+      // later gpu_actor_host_reserve succeeds (launch_step)
+      (void)upload_types();
+      return GPU_ACTOR_ENOMEM;
+    }
+  }
+  const int urc = upload_types();
+  return rc ? rc : urc;
+}
+
+GPU_ACTOR_API int gpu_actor_recv(gpu_host_msg_t* out, uint64_t cap, uint64_t* n)
+{
+  std::lock_guard<std::mutex> lk(g.mu);
+  if(!g.init) return GPU_ACTOR_ESTATE;
+  if(!n || (cap && !out)) return GPU_ACTOR_EINVAL;
+  *n = 0;
+  const int rc = observe();
+  if(rc) return rc;
+  const uint64_t k = std::min<uint64_t>(cap, g.hostq.size() - g.hostq_head);
+  if(k) memcpy(out, g.hostq.data() + g.hostq_head, k * sizeof(gpu_host_msg_t));
+  g.hostq_head += k;
+  if(g.hostq_head == g.hostq.size())
+  {
+    g.hostq.clear();
+    g.hostq_head = 0;
+  }
+  *n = k;
+  return 0;
+}
+
+GPU_ACTOR_API int gpu_actor_recv_pending(uint64_t* n)
+{
+  std::lock_guard<std::mutex> lk(g.mu);
+  if(!g.init) return GPU_ACTOR_ESTATE;
+  if(!n) return GPU_ACTOR_EINVAL;
+  *n = 0;
+  const int rc = observe();
+  if(rc) return rc;
+  *n = g.hostq.size() - g.hostq_head;
+  return 0;
+}
+
+GPU_ACTOR_API int gpu_actor_host_notify(gpu_actor_host_fn fn, void* ctx)
+{
+  std::lock_guard<std::mutex> lk(g.mu);
+  if(!g.init) return GPU_ACTOR_ESTATE;
+  g.host_fn = fn;
+  g.host_ctx = fn ? ctx : nullptr;
+  return 0;
+}
 
 // Diagnostic (not in the public header): engine internals for tests.
 // out[0] spill fixups, [1] k_sparse launches, [2] supersteps run by k_sparse,

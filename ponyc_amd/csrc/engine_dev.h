@@ -19,7 +19,14 @@
 #include <hip/hip_runtime.h>
 #endif
 #include <stdint.h>
+// (the run-time compiler gets the header by its plain name: a name with ../
+// would be unpacked outside that compilation's own directory, at one path
+// for every process compiling at the time, which rewrite it under each other)
+#ifdef __HIPCC_RTC__
+#include "gpu_actor.h"
+#else
 #include "../../include/gpu_actor.h"
+#endif
 #include "rng_dev.h"
 
 namespace gpa {
@@ -265,7 +272,26 @@ struct EngDev {
   // (their stores, and the owner's loads, at system scope: xrec_put/xrec_get)
   XRec* xdst[kMaxRanks];
   uint32_t peer_write, pad9;
+  // host ports (include/gpu_actor_host.h; send_host below): the id ranges of
+  // the port types (host_rng[0 .. host_nrng)) and the range that covers them
+  // all, [host_first, host_first + host_span) — span 0 without ports, so a
+  // program's SEND tests one range. The messages are listed in kHostShards
+  // segments of host_seg records (a wave lists into its own segment, one
+  // atomic on host_n[segment] per wave, and moves on to the next when that is
+  // full): host_key the canonical key *host_step | from << 16 | seq, host_rec
+  // {to, behaviour, arg}. host_step: the step's index since the last
+  // collection, shifted above the sender bits (k_host_begin writes it before
+  // every step of an engine with ports). The host compacts, sorts and gathers
+  // them after the step (engine.hip host_collect).
+  uint32_t host_first, host_span;
+  uint32_t host_nrng, host_seg;
+  struct HostRng { uint32_t first, count, type, pad; } host_rng[GPU_ACTOR_MAX_TYPES];
+  uint64_t* host_key;
+  uint4* host_rec;
+  unsigned int* host_n;           // [kHostShards] records listed (may count past host_seg)
+  const uint64_t* host_step;
 };
+constexpr uint32_t kHostShards = 64;
 constexpr uint32_t kGupsShards = 64;
 constexpr uint32_t kShards = 32;
 // landed records that make a zone hot (hot_dev.h). k_step consumes a prepared
@@ -387,6 +413,9 @@ struct ActorBase {
   // nor mute (the two-pass path: no backpressure anywhere, the zone's whole
   // mail below seq_max) — send_serial then skips both checks
   static constexpr bool kPlain = false;
+  // kHostPorts: a context whose program SENDs may address host ports
+  // (send_program); k_sparse's does not
+  static constexpr bool kHostPorts = true;
 
   __device__ __forceinline__ void reset_common()
   {
@@ -621,6 +650,97 @@ __device__ __forceinline__ void spawn_actor(A& a, uint32_t type, uint32_t beh, u
 __device__ __forceinline__ bool is_remote(uint32_t to)
 {
   return c_eng.nranks > 1 && rmod(to) != c_eng.rank;
+}
+
+// A program's SEND to a host port (include/gpu_actor_host.h): pony_sendv
+// towards a CPU actor (actor.c:773-817). Called for a target inside the
+// range that covers the port types; false when it is no port after all (a
+// type between two port types): the caller then sends it like any message.
+// The message takes the sender's next sequence number and counts as sent;
+// it counts at once as delivered under the port's own type (a lane may send
+// to ports of two types in one drain, so the by-type count does not go
+// through the drain's one cached applied_type: one add per wave and type to
+// the step's sharded counters); it is never parked in the outbox, never
+// mutes, never crosses ranks — the sender's rank lists it, whatever the
+// port's id % n_ranks. Listing: the wave's lanes that send reserve their
+// places with one atomic (ballot + mbcnt) on the wave's own segment; a full
+// segment passes the lanes without a place on to the next one, so messages
+// are lost (and counted) only when every segment is full. Key and payload
+// go out as vector stores; the host makes the list canonical after the step.
+template <class A>
+__device__ __forceinline__ bool send_host(A& a, uint32_t to, uint32_t beh, uint64_t arg)
+{
+  int t = -1;
+  for(uint32_t k = 0; k < c_eng.host_nrng; ++k)
+    if(to - c_eng.host_rng[k].first < c_eng.host_rng[k].count) t = (int)c_eng.host_rng[k].type;
+  if(t < 0) return false;
+  a.sent++;
+  const bool ok = a.seq < c_eng.seq_max;
+  if(!ok) atomicAdd(&c_eng.stats[ST_SEQ_OVERFLOW], 1ull);
+  const uint32_t seq = a.seq;
+  if(ok) a.seq++;
+  const uint32_t lane = __lane_id();
+  const uint32_t wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  // delivered, and delivered_by_type: one add per wave, and one per (wave,
+  // port type), straight to the step's sharded counters. They never pass
+  // through a.applied: the drain folds a thread's whole applied count under
+  // the one applied_type it cached — another actor's Analyzer or Updater type
+  // in a mixed zone
+  unsigned long long rest = __ballot(ok);
+  if(rest != 0ull && (int)lane == __ffsll((long long)rest) - 1)
+    atomicAdd(&c_eng.stats_sh[(size_t)ST_DELIVERED * kShards + (wave & (kShards - 1u))],
+      (unsigned long long)__popcll(rest));
+  while(rest != 0ull)
+  {
+    const int leader = __ffsll((long long)rest) - 1;
+    const int tl = __builtin_amdgcn_readlane(t, leader);
+    const unsigned long long peers = __ballot(ok && t == tl);
+    if((int)lane == leader)
+      atomicAdd(&c_eng.stats_sh[(size_t)(ST_BY_TYPE + tl) * kShards + (wave & (kShards - 1u))],
+        (unsigned long long)__popcll(peers));
+    rest &= ~peers;
+  }
+  // a place in the list
+  bool need = ok;
+  unsigned long long pend = __ballot(need);
+  uint32_t sh = wave & (kHostShards - 1u);
+  const uint32_t seg = c_eng.host_seg;
+  for(uint32_t tries = 0; tries < kHostShards && pend != 0ull; ++tries)
+  {
+    const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(pend >> 32),
+      __builtin_amdgcn_mbcnt_lo((uint32_t)pend, 0u));
+    const int leader = __ffsll((long long)pend) - 1;
+    unsigned int base = seg;
+    if((int)lane == leader &&
+       __hip_atomic_load(&c_eng.host_n[sh], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < seg)
+      base = atomicAdd(&c_eng.host_n[sh], (unsigned int)__popcll(pend));
+    base = __builtin_amdgcn_readlane(base, leader);
+    const uint32_t i = base + below;
+    if(need && base < seg && i < seg)
+    {
+      const size_t at = (size_t)sh * seg + i;
+      c_eng.host_key[at] = *c_eng.host_step | ((uint64_t)a.self << 16) | seq;
+      c_eng.host_rec[at] = make_uint4(to, beh, (uint32_t)arg, (uint32_t)(arg >> 32));
+      need = false;
+    }
+    pend = __ballot(need);
+    sh = (sh + 1u) & (kHostShards - 1u);
+  }
+  if(need) atomicAdd(&c_eng.stats[ST_DROPPED], 1ull);
+  return true;
+}
+
+// A program's SEND (the interpreter below, and the run-time compiled
+// programs, jit_host.h): one range test of the target against the port
+// types' ids; every other target goes through send_serial as before. A
+// context without kHostPorts (k_sparse's: an engine with ports never takes
+// the small-step path) compiles the plain send alone.
+template <class A>
+__device__ __forceinline__ void send_program(A& a, uint32_t to, uint32_t beh, uint64_t arg)
+{
+  if constexpr(A::kHostPorts)
+    if(to - c_eng.host_first < c_eng.host_span && send_host(a, to, beh, arg)) return;
+  send_serial(a, to, beh, arg);
 }
 
 // fan-in Analyzer apply, aggregated per wavefront: lanes hitting the same
@@ -951,7 +1071,7 @@ __device__ __forceinline__ void handle(HtTag<GPU_ACTOR_HT_PROGRAM>, const TypeDe
     if(op == GPU_ACTOR_OP_SEND)
     {
       if(x < c_eng.n_ids)
-        send_serial(a, (uint32_t)x, (uint32_t)imm & 15u, y);
+        send_program(a, (uint32_t)x, (uint32_t)imm & 15u, y);
       else
         atomicAdd(&c_eng.stats[ST_DROPPED], 1ull);
       continue;

@@ -123,6 +123,8 @@ inline std::string prog_function(const Prog& p)
       case GPU_ACTOR_OP_JNZ:   s += "  if(" + x + " != 0) goto " + target() + ";\n"; break;
       case GPU_ACTOR_OP_JMP:   s += "  goto " + target() + ";\n"; break;
       case GPU_ACTOR_OP_SEND:
+        // (in the device unit send_serial here is send_program, which takes a
+        // host port's id to send_host: unit_source)
         s += "  if(" + x + " < (uint64_t)c_eng.n_ids) send_serial(a, (uint32_t)" + x + ", " +
              std::to_string((uint32_t)imm & 15u) + "u, " + y +
              ");\n  else atomicAdd(&c_eng.stats[ST_DROPPED], 1ull);\n";
@@ -160,6 +162,12 @@ inline std::string unit_source(const std::vector<Prog>& progs, bool z12)
     s += "#define GPA_ZONE_BITS 12\n#define GPA_ZONE_THREADS 1024\n#define GPA_IDX_CAP 24576\n"
          "#define GPA_TILE 7168\n";
   s += "#include \"zone_dev.h\"\nnamespace gpa {\n";
+  // A program's SEND is send_program (engine_dev.h: a host port's id goes to
+  // send_host, every other target to send_serial). The generated functions
+  // keep the one name for a send, so that they also compile against a host
+  // stand-in of the device side that knows no ports; here, behind every
+  // header, that name is send_program.
+  s += "#define send_serial(a, to, beh, arg) send_program(a, to, beh, arg)\n";
   for(const Prog& p : progs) s += prog_function(p);
   s += "template <class A>\n__device__ __forceinline__ void handle(HtTag<kHtJit>, const TypeDev& T, A& a,\n"
        "  uint64_t (&s)[8], uint32_t beh, uint64_t arg)\n{\n  switch(a.type)\n  {\n";

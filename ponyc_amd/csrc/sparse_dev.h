@@ -71,6 +71,8 @@ __device__ __forceinline__ int sp_type(const SpType* ti, uint32_t n_types, uint3
 }
 
 struct SparseCtx : ActorBase {
+  // engines with host ports stay on the zone path (engine.hip sparse_ok)
+  static constexpr bool kHostPorts = false;
   SpList nx;              // the next step's list
   uint32_t q;             // its length is sp_cnt[q] (may count past kSpCap)
   uint32_t* s_over;       // set when it overflowed into landing[nxt]

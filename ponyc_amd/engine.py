@@ -91,6 +91,17 @@ EXPORTS = [
     "gpu_actor_set_transport", "gpu_actor_run_async", "gpu_actor_wait", "gpu_actor_busy",
 ]
 
+# messages to the host (include/gpu_actor_host.h): every symbol that header declares
+HT_HOST_PORT = 14
+HOST_RESERVE_DEFAULT = 1 << 20
+HOST_MSG_DTYPE = np.dtype([("step", "<u8"), ("from", "<u4"), ("seq", "<u4"), ("to", "<u4"),
+                           ("behaviour", "<u4"), ("arg", "<u8")])
+HOST_EXPORTS = [
+    "gpu_actor_host_reserve", "gpu_actor_recv", "gpu_actor_recv_pending", "gpu_actor_host_notify",
+]
+# (include/gpu_actor_host.h: gpu_actor_host_fn)
+HOST_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64)
+
 # host-transport callbacks (include/gpu_actor.h: gpu_actor_alltoallv_fn / _allreduce_fn)
 ALLTOALLV_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                 ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p,
@@ -145,6 +156,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "gpu_actor_run_async": (i32, [u64, DONE_FN, vp]),
         "gpu_actor_wait": (i32, [ctypes.POINTER(u64)]),
         "gpu_actor_busy": (i32, []),
+        # include/gpu_actor_host.h
+        "gpu_actor_host_reserve": (i32, [u64]),
+        "gpu_actor_recv": (i32, [vp, u64, ctypes.POINTER(u64)]),
+        "gpu_actor_recv_pending": (i32, [ctypes.POINTER(u64)]),
+        "gpu_actor_host_notify": (i32, [HOST_FN, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -233,6 +249,7 @@ class Engine:
         self.count: dict[int, int] = {}
         self.reserve: dict[int, int] = {}
         self._thunks: list = []
+        self._host_thunk = None
         self.alive = True
 
     @staticmethod
@@ -372,6 +389,46 @@ class Engine:
             "delivered_by_type": [c.delivered_by_type[i] for i in range(MAX_TYPES)],
             "atomics": c.atomics,
         }
+
+    # -- messages to the host (include/gpu_actor_host.h) ---------------------------
+    def host_reserve(self, n: int) -> None:
+        """Device room for n host-bound messages per collection."""
+        _ck("gpu_actor_host_reserve", self.lib.gpu_actor_host_reserve(n))
+
+    def recv_pending(self) -> int:
+        n = ctypes.c_uint64(0)
+        _ck("gpu_actor_recv_pending", self.lib.gpu_actor_recv_pending(ctypes.byref(n)))
+        return n.value
+
+    def recv(self, cap: int | None = None) -> np.ndarray:
+        """Up to `cap` (default: all) of the oldest messages behaviours sent to
+        host ports, in canonical (step, from, seq) order: a HOST_MSG_DTYPE array."""
+        if cap is None:
+            cap = self.recv_pending()
+        out = np.zeros(cap, dtype=HOST_MSG_DTYPE)
+        n = ctypes.c_uint64(0)
+        _ck("gpu_actor_recv",
+            self.lib.gpu_actor_recv(out.ctypes.data_as(ctypes.c_void_p), cap, ctypes.byref(n)))
+        return out[:n.value]
+
+    def host_notify(self, fn) -> None:
+        """fn(msgs: HOST_MSG_DTYPE array) takes every collection's messages
+        instead of the queue, on the thread that runs the steps; it must not
+        call into the engine. None restores the queue."""
+        if fn is None:
+            _ck("gpu_actor_host_notify", self.lib.gpu_actor_host_notify(HOST_FN(), None))
+            self._host_thunk = None
+            return
+
+        def _cb(_ctx, msgs, n):
+            try:
+                buf = (ctypes.c_uint8 * (int(n) * HOST_MSG_DTYPE.itemsize)).from_address(msgs)
+                fn(np.frombuffer(buf, dtype=HOST_MSG_DTYPE).copy())
+            except Exception as e:  # never let an exception cross the C boundary
+                print(f"gpu_actor host_notify callback failed: {e!r}")
+        thunk = HOST_FN(_cb)
+        _ck("gpu_actor_host_notify", self.lib.gpu_actor_host_notify(thunk, None))
+        self._host_thunk = thunk      # the library holds the pointer until it is replaced
 
     def debug_info(self) -> dict:
         """Engine internals (diagnostic export, not in include/gpu_actor.h)."""

@@ -153,6 +153,54 @@ def det_program(beh: int = 0) -> np.ndarray:
     return p.assemble()
 
 
+def emitter_program(ports_param: int = 0, n_ports_param: int = 1, magic_param: int = 2,
+                    first_param: int = 3, bursts_param: int = 4) -> np.ndarray:
+    """An actor that reports to host ports (include/gpu_actor_host.h; the
+    shape of the FIFO probe's source, with the ports in the sinks' place).
+    Behaviour 0 BURST(m): m times, bump the counter c (word 1) and SEND
+    behaviour 0 (PUSH) with argument index << 32 | c to port
+    param[ports] + (index + c) % param[n_ports]; then count the burst (word 2)
+    and re-send BURST(m) to itself while fewer than param[bursts] are done.
+    index = self - param[first]. The ISA has no division: the modulus goes
+    through param[magic] = floor(2^64 / P) + 1 (exact for 32-bit operands;
+    unused when P == 1)."""
+    p = Program()
+    p.behaviour(0)
+    p.ldp(11, first_param)
+    p.sub(11, R_SELF, 11)               # index
+    p.mov(12, R_ARG)                    # sends left in this burst
+    p.label("loop")
+    p.jz(12, "done")
+    p.addi(1, 1, 1)                     # c
+    p.ldi(13, 0)
+    p.ldp(15, n_ports_param)
+    p.addi(14, 15, -1)
+    p.jz(14, "one")                     # one port: offset 0
+    p.add(13, 11, 1)                    # x = index + c
+    p.ldp(14, magic_param)
+    p.mulhi(14, 13, 14)                 # x / P
+    p.mul(14, 14, 15)
+    p.sub(13, 13, 14)                   # x % P
+    p.label("one")
+    p.ldp(14, ports_param)
+    p.add(13, 13, 14)                   # the port
+    p.ldi(14, 32)
+    p.shl(14, 11, 14)
+    p.or_(14, 14, 1)                    # index << 32 | c
+    p.send(13, 0, 14)
+    p.addi(12, 12, -1)
+    p.jmp("loop")
+    p.label("done")
+    p.addi(2, 2, 1)
+    p.ldp(14, bursts_param)
+    p.ltu(15, 2, 14)
+    p.jz(15, "end")
+    p.send(R_SELF, 0, R_ARG)
+    p.label("end")
+    p.halt()
+    return p.assemble()
+
+
 def spreader_program(type_id: int) -> np.ndarray:
     """examples/spreader/main.pony:1-48 (the compiled GPU_ACTOR_HT_SPREADER,
     engine_dev.h) for a program type `type_id`: word 0 count, 1 parent (~0:

@@ -279,3 +279,48 @@ def fifo(eng, sources: int = 64, sinks: int = 8, bursts: int = 10, m: int = 4,
 
 def fifo_result(eng, w: dict) -> np.ndarray:
     return eng.state_read(w["sink_type"])
+
+
+# ---- actors that report to the host (include/gpu_actor_host.h) --------------------------------
+def emitter(eng, n: int = 3000, ports=(3, 1), bursts: int = 3, m=None, batch: int = 0,
+            port_ht: int | None = None, port_words: int = 11, port_batch: int = 0,
+            emit_type: int = 0, port_type0: int = 1, initial: int = 1) -> dict:
+    """`n` program actors (ponyc_amd.program.emitter_program), then one port
+    type per entry of `ports` with that many ports, their ids consecutive.
+    Every emitter gets BURST(m), `initial` times: `m` an int, or None for
+    index % 4 (with a small `batch`, more than one leaves mail carried over
+    steps and the emitters overloaded). `port_ht`
+    is the ports' handler table: HT_HOST_PORT (default) in the engine; the
+    oracle registers a stand-in there (HT_FANIN_ANALYZER, or HT_FIFO_SINK with
+    `port_batch` above the run's messages) with the same types and ids.
+    `batch`: the emitters' per-step drain limit (0: the default)."""
+    from .engine import HT_HOST_PORT
+    if port_ht is None:
+        port_ht = HT_HOST_PORT
+    eng.type_register(emit_type, 8, HT_PROGRAM)
+    eng.type_program(emit_type, P.emitter_program())
+    if batch:
+        eng.type_config(emit_type, batch, 0)
+    first = eng.create(emit_type, n)
+    total = int(sum(ports))
+    pfirst = []
+    for k, cnt in enumerate(ports):
+        t = port_type0 + k
+        eng.type_register(t, port_words, port_ht)
+        if port_batch:
+            eng.type_config(t, port_batch, 0)
+        if port_ht == HT_FIFO_SINK:
+            eng.type_param(t, 0, n)     # one slot for every emitter index
+        pfirst.append(eng.create(t, cnt))
+    assert all(pfirst[k] + ports[k] == pfirst[k + 1] for k in range(len(ports) - 1))
+    eng.type_param(emit_type, 0, pfirst[0])
+    eng.type_param(emit_type, 1, total)
+    eng.type_param(emit_type, 2, ((1 << 64) // total + 1) & 0xFFFFFFFFFFFFFFFF)
+    eng.type_param(emit_type, 3, first)
+    eng.type_param(emit_type, 4, bursts)
+    i = np.tile(np.arange(n, dtype=np.uint64), initial)
+    arg = i % np.uint64(4) if m is None else np.full(i.shape[0], m, dtype=np.uint64)
+    _sendv(eng, _msgs(first + i, 0, arg))
+    return {"emit_type": emit_type, "port_types": [port_type0 + k for k in range(len(ports))],
+            "first": first, "n": n, "pfirst": pfirst, "ports": list(ports), "n_ports": total,
+            "port_first": pfirst[0], "bursts": bursts}

@@ -24,6 +24,8 @@ def sets():
         out.append(([(0, P.ring_program())], z12))
         out.append(([(0, P.det_program(0))], z12))
         out.append(([(0, P.spreader_program(0))], z12))
+        # the host-port tests' emitters (tests/test_gpu_host_port.py)
+        out.append(([(0, P.emitter_program())], z12))
     out.append(([(0, edge_program())], False))
     # any-mix engines of the tests (bit per table id): ring + FIFO source +
     # sink (test_hot_zones_past_kmaxhot), ring + spreader + fan-in sender
