@@ -20,6 +20,7 @@
 #include <condition_variable>
 #include <map>
 #include <mutex>
+#include <new>
 #include <thread>
 #include <vector>
 
@@ -30,6 +31,7 @@
 #include "hot_dev.h"
 #include "step_entry.h"
 #include "jit_host.h"
+#include "dev_buf.h"
 
 // the 4096-actor-zone instantiations (step_*_z12.hip)
 namespace gpa_z12 {
@@ -327,14 +329,42 @@ struct HostType {
   uint32_t lfirst = 0, lcount = 0;
   uint64_t reserve = 0;                 // ids for actors spawned by behaviours
   int32_t priority = 0;                 // the fork's _priority() hint
-  uint64_t* d_state = nullptr;
-  uint64_t* d_prog = nullptr;           // GPU_ACTOR_HT_PROGRAM: the behaviours' program
+  DevBuf<uint64_t> d_state;
+  DevBuf<uint64_t> d_prog;              // GPU_ACTOR_HT_PROGRAM: the behaviours' program
   uint32_t prog_n = 0;
   bool prog_yields = false;             // it holds a YIELD or a SPAWN: the small-step path leaves it
   std::vector<uint64_t> prog_host;      // the program's words (the run-time compiled step, jit_host.h)
 };
 
-struct Engine {
+// Records past zone capacity: the spill lists' counters (Session::d_sstat)
+struct SpillStat {
+  unsigned int spill_n[2];
+  unsigned int halt;
+  unsigned int pad;
+  unsigned long long skipped;
+};
+
+// The hot-zone scratch words (hot_dev.h) of Session::d_hot, as word offsets in
+// the order the device's arrays lie: upload_types hands them to the device,
+// init fills the aux key ranges. bar is the grid barrier's [0] arrivals, [1]
+// finished workgroups, [2] missed phases, [3] zones given back after a miss.
+struct HotLayout {
+  size_t prep = 0;
+  size_t slot = prep + kMaxZones;
+  size_t cnt = slot + kMaxZones;
+  size_t aux = cnt + (size_t)kMaxHot * kHotActors;        // kMaxHot x 3 x kHotActors
+  size_t hist = aux + (size_t)kMaxHot * 3 * kHotActors;
+  size_t bcnt = hist + kHotBins;
+  size_t cur = bcnt + kHotBins;                           // kHotBins + kHotActors
+  size_t bar = cur + kHotBins + kHotActors;
+  size_t words = bar + 64;
+};
+constexpr HotLayout kHotLayout{};
+
+// What lives across gpu_actor_init / gpu_actor_shutdown: the locks, the
+// progress threads of asynchronous runs, and the host transport (set before
+// init, kept by shutdown).
+struct Process {
   std::mutex mu;
   // asynchronous run (gpu_actor_run_async): one progress thread at a time;
   // wmu guards the thread object (joined or detached by whoever reaps it)
@@ -347,6 +377,17 @@ struct Engine {
   std::atomic<bool> async_started{false};  // the progress thread holds mu
   int async_rc = 0;
   uint64_t async_steps = 0;
+  // host transport (gpu_actor_set_transport)
+  gpu_actor_alltoallv_fn xp_a2a = nullptr;
+  gpu_actor_allreduce_fn xp_ar = nullptr;
+  void* xp_ctx = nullptr;
+};
+
+// One engine, from gpu_actor_init to gpu_actor_shutdown (or to a failed init):
+// every field starts from its initialiser here, the buffers free themselves
+// (dev_buf.h), and session_end() replaces the whole value — nothing below is
+// named in a teardown list.
+struct Session {
   bool init = false;
   gpu_actor_config_t cfg{};
   int device = 0;
@@ -358,28 +399,28 @@ struct Engine {
   // zones
   uint32_t n_zones = 0;
   uint64_t zone_records = 0;
-  uint64_t* d_zoff = nullptr;
-  uint32_t* d_zcap = nullptr;
-  ZRec* d_land[2] = {nullptr, nullptr};
-  ZRec* d_carry[2] = {nullptr, nullptr};
-  uint32_t* d_land_n[2] = {nullptr, nullptr};
-  uint32_t* d_carry_n[2] = {nullptr, nullptr};
-  ZRec* d_S = nullptr;
-  ORec* d_O = nullptr;
+  DevBuf<uint64_t> d_zoff;
+  DevBuf<uint32_t> d_zcap;
+  DevBuf<ZRec> d_land[2], d_carry[2];
+  DevBuf<uint32_t> d_land_n[2], d_carry_n[2];
+  DevBuf<ZRec> d_S;
+  DevBuf<ORec> d_O;
   uint32_t par = 0;                     // parity the next step reads
-  unsigned long long* d_stats = nullptr;
-  unsigned long long* d_pend = nullptr;
-  unsigned long long* d_pend_sh = nullptr;    // [kPendSlots][kShards]: k_step's adds
-  unsigned long long* d_stats_sh = nullptr;   // [ST_COUNT][kShards]
+  DevBuf<unsigned long long> d_stats;
+  DevBuf<unsigned long long> d_pend;
+  DevBuf<unsigned long long> d_pend_sh;    // [kPendSlots][kShards]: k_step's adds
+  DevBuf<unsigned long long> d_stats_sh;   // [ST_COUNT][kShards]
   // hot zones (hot_dev.h k_hot): one allocation, carved into EngDev's arrays
-  uint32_t* d_hot = nullptr;
+  // (HotLayout)
+  DevBuf<uint32_t> d_hot;
   bool hot_on = false;
-  unsigned long long* d_dbg = nullptr;   // phase stamps of the diagnostic build
-  gpu_msg_t* h_msgs = nullptr; uint64_t h_msgs_cap = 0;
+  int hot_fits = -1;                    // hot_resident()'s answer (-1: not asked yet)
+  DevBuf<unsigned long long> d_dbg;     // phase stamps of the diagnostic build
+  PinBuf<gpu_msg_t> h_msgs;
   // gpu_actor_send appends here; flushed (one H2D + k_inject) before the
   // next operation that observes device state, so a send costs no sync
   std::vector<gpu_msg_t> deferred;
-  gpu_msg_t* d_msgs = nullptr; uint64_t d_msgs_cap = 0;
+  DevBuf<gpu_msg_t> d_msgs;
   uint64_t host_seq = 0;
   uint64_t steps_total = 0;
   int sticky = 0;
@@ -392,23 +433,21 @@ struct Engine {
   uint64_t jit_failed = 0;
   uint32_t jit_builds = 0;
   bool jit_used = false;                // the last step ran the compiled module
-  TypeDev td_host[GPU_ACTOR_MAX_TYPES];
-  EngDev eng_host;
+  TypeDev td_host[GPU_ACTOR_MAX_TYPES] = {};
+  EngDev eng_host = {};
   bool consts_host = false;
   // GUPS streamers' chunks for k_gups_apply (EngDev::gups_*; gups_type -1: none)
-  uint64_t* d_gups_list = nullptr;
-  unsigned int* d_gups_n = nullptr;
-  uint64_t* d_gups_jump = nullptr;
-  unsigned long long* d_gups_stat = nullptr;
+  DevBuf<uint64_t> d_gups_list;
+  DevBuf<unsigned int> d_gups_n;
+  DevBuf<uint64_t> d_gups_jump;
+  DevBuf<unsigned long long> d_gups_stat;
   uint64_t gups_jump_host[65] = {};
-  uint32_t gups_cap = 0;
   int gups_type = -1;
   // n_ranks > 1: this rank's chunks packed to one run (k_gups_pack), every
   // rank's runs gathered in rank order for k_gups_apply_ranks; chunks received
   // from peers and listed here since init (gpu_actor_debug_info)
-  uint64_t* d_gups_send = nullptr;
-  uint64_t* d_gups_all = nullptr;
-  uint64_t gups_all_cap = 0;
+  DevBuf<uint64_t> d_gups_send;
+  DevBuf<uint64_t> d_gups_all;
   uint32_t gups_parts = 0;
   uint64_t gups_in_total = 0, gups_out_total = 0;
   // One rank: device work that can change the spill status or the counters
@@ -421,19 +460,18 @@ struct Engine {
   double last_drain_ms = 0.0;
   // multi-rank exchange
   ncclComm_t comm = nullptr;
-  XRec* d_xout = nullptr;
-  XRec* d_xin = nullptr;
+  DevBuf<XRec> d_xout;
+  DevBuf<XRec> d_xin;
   // [3R + 3]: send counts, receive counts, two scratch words, the GUPS chunks
   // this rank listed in the step (k_gups_pack), every rank's such count
-  unsigned long long* d_xc = nullptr;
+  DevBuf<unsigned long long> d_xc;
   unsigned long long* d_xcount = nullptr;  // d_xc
   unsigned long long* d_xrecv = nullptr;   // d_xc + R
-  unsigned long long* h_xc = nullptr;      // pinned mirror of d_xc
-  unsigned int* d_spill_flag = nullptr;    // spill lists in use on any rank (summed)
+  PinBuf<unsigned long long> h_xc;         // pinned mirror of d_xc
+  DevBuf<unsigned int> d_spill_flag;       // spill lists in use on any rank (summed)
   uint32_t xcap = 0;                       // records per peer segment of xout
-  uint64_t xin_cap = 0;                    // records d_xin (and h_xin) hold
-  XSpillRec* d_xspill = nullptr;           // cross-rank records past xcap
-  unsigned int* d_xspill_n = nullptr;
+  DevBuf<XSpillRec> d_xspill;              // cross-rank records past xcap
+  DevBuf<unsigned int> d_xspill_n;
   uint32_t xspill_cap = 0;
   std::vector<unsigned long long> h_xcount, h_xrecv;   // host transport
   uint64_t remote_total = 0;
@@ -441,67 +479,52 @@ struct Engine {
   // inbox [R][xcap] (segment p: peer p's records, stored by peer p's k_step),
   // every peer's inbox mapped over IPC, and a small collective scratch
   bool peer_write = false;
-  XRec* d_pin = nullptr;
+  DevBuf<XRec> d_pin;
   XRec* peer_ptr[kMaxRanks] = {};
-  unsigned long long* d_hx = nullptr;      // [1 + R]
-  // host transport (gpu_actor_set_transport)
-  gpu_actor_alltoallv_fn xp_a2a = nullptr;
-  gpu_actor_allreduce_fn xp_ar = nullptr;
-  void* xp_ctx = nullptr;
+  DevBuf<unsigned long long> d_hx;         // [1 + R]
   // host transport staging (pinned): what this rank sends, what it receives
-  uint8_t* h_sbuf = nullptr;
-  uint8_t* h_rbuf = nullptr;
-  uint64_t h_sbuf_cap = 0, h_rbuf_cap = 0;
+  PinBuf<uint8_t> h_sbuf, h_rbuf;
   // spawned actors (gpu_actor_type_reserve)
   uint32_t spawn_cap = 0;
-  uint64_t *d_skey[2] = {nullptr, nullptr}, *d_sarg[2] = {nullptr, nullptr};
-  unsigned int* d_spawn_n = nullptr;
-  uint32_t *d_tstart = nullptr, *d_tcnt = nullptr;
-  unsigned long long* d_live = nullptr;  // [GPU_ACTOR_MAX_TYPES] live actors per type
-  void* d_sort_tmp = nullptr;
-  size_t sort_tmp_bytes = 0;
-  // records past zone capacity: spill lists, their counters, and the minimum
-  // capacity each zone has grown to
-  struct SpillStat {
-    unsigned int spill_n[2];
-    unsigned int halt;
-    unsigned int pad;
-    unsigned long long skipped;
-  };
+  DevBuf<uint64_t> d_skey[2], d_sarg[2];
+  DevBuf<unsigned int> d_spawn_n;
+  DevBuf<uint32_t> d_tstart, d_tcnt;
+  DevBuf<unsigned long long> d_live;     // [GPU_ACTOR_MAX_TYPES] live actors per type
+  DevBuf<uint8_t> d_sort_tmp;            // hipcub's scratch (sort_room)
   // backpressure: trigger bytes per global id and parity
   // (d_trig_own: this rank's own bytes when n_ranks > 1, merged into d_trig),
   // the receiver each muted local actor waits on, per-zone trigger counts,
   // per-step counts (index = step mod 3), and the step index
-  uint8_t* d_trig[2] = {nullptr, nullptr};
-  uint8_t* d_trig_own[2] = {nullptr, nullptr};
+  DevBuf<uint8_t> d_trig[2], d_trig_own[2];
   uint64_t trig_bytes = 0;
   bool trig_stale[2] = {false, false};
-  uint32_t* d_muted_on = nullptr;
-  uint64_t muted_on_cap = 0;
-  uint32_t* d_ztrig[2] = {nullptr, nullptr};
-  unsigned int* d_trig_n = nullptr;
+  DevBuf<uint32_t> d_muted_on;
+  DevBuf<uint32_t> d_ztrig[2];
+  DevBuf<unsigned int> d_trig_n;
   // zones the step's two-pass launch ran (EngDev::zplan); split_plan: run a
   // two-pass table's step as the two launches (PONYC_AMD_SPLIT_PLAN=0: one)
-  uint32_t* d_zplan = nullptr;
+  DevBuf<uint32_t> d_zplan;
   bool split_plan = true;
   // split tables: the step as one launch (k_step PM 3: the rest through a
   // call) instead of two (PONYC_AMD_FUSE=0: two)
   bool fuse = true;
   uint32_t sidx = 0;
   // backlog copies handed to k_carry_big (EngDev::bigc)
-  BigCopy* d_bigc = nullptr;
-  unsigned long long* d_bigc_n = nullptr;
+  DevBuf<BigCopy> d_bigc;
+  DevBuf<unsigned long long> d_bigc_n;
   bool defer_big = false;
-  SpillRec* d_spill[2] = {nullptr, nullptr};
+  // records past zone capacity: spill lists, their counters, and the minimum
+  // capacity each zone has grown to
+  DevBuf<SpillRec> d_spill[2];
   uint32_t spill_cap = 0;
-  SpillStat* d_sstat = nullptr;
-  SpillStat* h_sstat = nullptr;           // pinned
-  uint32_t* d_need = nullptr;
+  DevBuf<SpillStat> d_sstat;
+  PinBuf<SpillStat> h_sstat;
+  DevBuf<uint32_t> d_need;
   std::vector<uint32_t> zcap_min, zcap_host;
   uint64_t fixups = 0;
   // small-step path (k_sparse)
-  SparseCtl* d_ctl = nullptr;
-  SparseCtl* h_ctl = nullptr;             // pinned
+  DevBuf<SparseCtl> d_ctl;
+  PinBuf<SparseCtl> h_ctl;
   uint64_t sparse_launches = 0, sparse_steps = 0;
   // zone geometry: actors per zone = 1 << zbits (step_entry.h; chosen by
   // relayout_zones)
@@ -518,14 +541,16 @@ struct Engine {
   uint32_t host_base = 0;
   uint64_t host_reserve = GPU_ACTOR_HOST_RESERVE_DEFAULT;
   uint32_t host_seg = 0, host_kshift = 48;
-  uint64_t *d_host_key = nullptr, *d_host_kc = nullptr, *d_host_ks = nullptr;
-  uint32_t *d_host_ic = nullptr, *d_host_is = nullptr;
-  uint4* d_host_rec = nullptr;
-  unsigned int* d_host_n = nullptr;
-  unsigned int* h_host_n = nullptr;        // pinned
-  uint64_t* d_host_step = nullptr;
-  gpu_host_msg_t* d_host_out = nullptr;
-  gpu_host_msg_t* h_host_out = nullptr;    // pinned
+  struct HostLists {                       // sized by host_reserve (host_alloc)
+    DevBuf<uint64_t> d_host_key, d_host_kc, d_host_ks;
+    DevBuf<uint32_t> d_host_ic, d_host_is;
+    DevBuf<uint4> d_host_rec;
+    DevBuf<gpu_host_msg_t> d_host_out;
+    PinBuf<gpu_host_msg_t> h_host_out;
+  } hl;
+  DevBuf<unsigned int> d_host_n;
+  PinBuf<unsigned int> h_host_n;
+  DevBuf<uint64_t> d_host_step;
   // collected messages not yet received (gpu_actor_recv), from hostq_head on;
   // or the callback that takes them instead (gpu_actor_host_notify)
   std::vector<gpu_host_msg_t> hostq;
@@ -534,7 +559,10 @@ struct Engine {
   void* host_ctx = nullptr;
 };
 
-Engine g;
+Process gp;
+// On the heap and never destroyed: a process that exits without
+// gpu_actor_shutdown runs no HIP call from a static destructor.
+Session& g = *new Session;
 
 #define HIPCK(expr)                                                    \
   do {                                                                 \
@@ -616,15 +644,7 @@ bool defer_big_wanted()
 
 StepEntry pick_step_entry();
 
-// The hot-zone scratch words (hot_dev.h), in the order upload_types hands
-// them to the device; hot_bar_words() is the grid barrier's [0] arrivals, [1]
-// finished workgroups, [2] missed phases, [3] zones given back after a miss.
-inline size_t hot_words_before_bar()
-{
-  return 2 * (size_t)kMaxZones + (size_t)kMaxHot * kHotActors + (size_t)kMaxHot * 3 * kHotActors +
-         3 * (size_t)kHotBins + kHotActors;
-}
-inline uint32_t* hot_bar_words() { return g.d_hot + hot_words_before_bar(); }
+inline uint32_t* hot_bar_words() { return g.d_hot + kHotLayout.bar; }
 
 // k_hot's workgroups must all be resident at once (its phases meet at grid
 // barriers, hot_dev.h): kHotBlocks workgroups of kHotThreads with the LDS of
@@ -634,7 +654,7 @@ inline uint32_t* hot_bar_words() { return g.d_hot + hot_words_before_bar(); }
 // MI355X_MICROARCH.md, so one is taken off). Asked once per engine.
 bool hot_resident()
 {
-  static int cached = -1;
+  int& cached = g.hot_fits;
   if(cached >= 0) return cached != 0;
   int per_cu = 0, cus = 0;
   const size_t lds = 5u * kHotActors * sizeof(uint32_t);
@@ -682,26 +702,21 @@ int gups_setup(EngDev& e)
   // kGupsShards segments, each at least 2^16 chunks (k_sparse lists from its
   // few waves' segments only)
   const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(1ull << 22, 2ull * h.lcount), 1ull << 28);
-  if(cap > g.gups_cap)
+  if(cap > g.d_gups_list.size())
   {
     HIPCK(hipStreamSynchronize(g.stream));      // no k_gups_apply still reads the old list
-    if(g.d_gups_list) HIPCK(hipFree(g.d_gups_list));
-    g.d_gups_list = nullptr;
-    g.gups_cap = 0;
-    HIPCK(hipMalloc(&g.d_gups_list, cap * sizeof(uint64_t)));
-    g.gups_cap = (uint32_t)cap;
+    HIPCK(g.d_gups_list.alloc(cap));
     // the packed run holds what the list holds (between steps both are empty)
-    if(g.d_gups_send) HIPCK(hipFree(g.d_gups_send));
-    g.d_gups_send = nullptr;
+    g.d_gups_send.reset();
   }
   if(R() > 1 && !g.d_gups_send)
-    HIPCK(hipMalloc(&g.d_gups_send, (size_t)g.gups_cap * sizeof(uint64_t)));
+    HIPCK(g.d_gups_send.alloc(g.d_gups_list.size()));
   if(!g.d_gups_n)
   {
-    HIPCK(hipMalloc(&g.d_gups_n, (kGupsShards + 1) * sizeof(unsigned int)));
+    HIPCK(g.d_gups_n.alloc(kGupsShards + 1));
     HIPCK(hipMemsetAsync(g.d_gups_n, 0, (kGupsShards + 1) * sizeof(unsigned int), g.stream));
-    HIPCK(hipMalloc(&g.d_gups_jump, 65 * sizeof(uint64_t)));
-    HIPCK(hipMalloc(&g.d_gups_stat, 3 * kGupsBlocks * sizeof(unsigned long long)));
+    HIPCK(g.d_gups_jump.alloc(65));
+    HIPCK(g.d_gups_stat.alloc(3 * kGupsBlocks));
     HIPCK(hipMemsetAsync(g.d_gups_stat, 0, 3 * kGupsBlocks * sizeof(unsigned long long), g.stream));
   }
   uint64_t jump[65] = {};
@@ -716,7 +731,7 @@ int gups_setup(EngDev& e)
   }
   e.gups_list = g.d_gups_list; e.gups_n = g.d_gups_n; e.gups_jump = g.d_gups_jump;
   e.gups_stat = g.d_gups_stat;
-  e.gups_seg = g.gups_cap / kGupsShards;
+  e.gups_seg = (uint32_t)(g.d_gups_list.size() / kGupsShards);
   {
     // (tests: PONYC_AMD_GUPS_SEG=n lists at most n chunks per segment, so that
     // full segments send the rest through the streamers' own path)
@@ -782,14 +797,9 @@ int upload_types()
   e.pend_sh = g.d_pend_sh; e.stats_sh = g.d_stats_sh;
   {
     uint32_t* h = g.d_hot;
-    e.hot_prep = h; h += kMaxZones;
-    e.hot_slot = h; h += kMaxZones;
-    e.hot_cnt = h; h += kMaxHot * kHotActors;
-    e.hot_aux = h; h += kMaxHot * 3 * kHotActors;
-    e.hot_hist = h; h += kHotBins;
-    e.hot_bcnt = h; h += kHotBins;
-    e.hot_cur = h; h += kHotBins + kHotActors;
-    e.hot_bar = h;
+    const HotLayout& L = kHotLayout;
+    e.hot_prep = h + L.prep; e.hot_slot = h + L.slot; e.hot_cnt = h + L.cnt; e.hot_aux = h + L.aux;
+    e.hot_hist = h + L.hist; e.hot_bcnt = h + L.bcnt; e.hot_cur = h + L.cur; e.hot_bar = h + L.bar;
   }
   e.xout = g.d_xout; e.xcount = g.d_xcount; e.xcap = g.xcap;
   e.peer_write = g.peer_write ? 1u : 0u;
@@ -856,7 +866,7 @@ int upload_types()
     e.host_first = e.host_nrng ? (uint32_t)lo : 0u;
     e.host_span = e.host_nrng ? (uint32_t)(hi - lo) : 0u;
     e.host_seg = g.host_seg;
-    e.host_key = g.d_host_key; e.host_rec = g.d_host_rec; e.host_n = g.d_host_n;
+    e.host_key = g.hl.d_host_key; e.host_rec = g.hl.d_host_rec; e.host_n = g.d_host_n;
     e.host_step = g.d_host_step;
   }
   {
@@ -885,12 +895,8 @@ int ensure_spill(uint64_t cap)
 {
   cap = std::min<uint64_t>(cap, 0x7FFFFFFFull);
   if(cap <= g.spill_cap) return 0;
-  for(int p = 0; p < 2; ++p)
-  {
-    if(g.d_spill[p]) HIPCK(hipFree(g.d_spill[p]));
-    g.d_spill[p] = nullptr;
-    HIPCK(hipMalloc(&g.d_spill[p], cap * sizeof(SpillRec)));
-  }
+  g.spill_cap = 0;
+  for(int p = 0; p < 2; ++p) HIPCK(g.d_spill[p].alloc(cap));
   g.spill_cap = (uint32_t)cap;
   return 0;
 }
@@ -909,7 +915,7 @@ inline uint64_t spill_cap_for_zones()
 
 int read_sstat()
 {
-  HIPCK(hipMemcpyAsync(g.h_sstat, g.d_sstat, sizeof(Engine::SpillStat), hipMemcpyDeviceToHost,
+  HIPCK(hipMemcpyAsync(g.h_sstat, g.d_sstat, sizeof(SpillStat), hipMemcpyDeviceToHost,
     g.stream));
   HIPCK(hipStreamSynchronize(g.stream));
   g.sstat_epoch = g.dev_epoch;
@@ -930,7 +936,7 @@ inline bool spill_pending()
 // with nothing of its own to land, so that every rank's next step runs alike.
 int fixup_spill()
 {
-  const Engine::SpillStat st = *g.h_sstat;
+  const SpillStat st = *g.h_sstat;
   g.dev_epoch++;
   if(R() == 1 && !st.spill_n[0] && !st.spill_n[1] && !st.halt) return 0;
   uint32_t n[2], most = 0;
@@ -974,10 +980,10 @@ int fixup_spill()
           (const SpillRec*)g.d_spill[p], n[p], (uint32_t)p);
     HIPCK(hipGetLastError());
   }
-  HIPCK(hipMemsetAsync(g.d_sstat, 0, sizeof(Engine::SpillStat), g.stream));
+  HIPCK(hipMemsetAsync(g.d_sstat, 0, sizeof(SpillStat), g.stream));
   HIPCK(hipMemsetAsync(g.d_spill_flag, 0, sizeof(unsigned int), g.stream));
   HIPCK(hipStreamSynchronize(g.stream));
-  memset(g.h_sstat, 0, sizeof(Engine::SpillStat));
+  memset(g.h_sstat, 0, sizeof(SpillStat));
   g.fixups++;
   // Only now, with every spilled record placed, may the lists be re-sized
   // (ensure_spill drops their contents): to the grown zones' share, and
@@ -1025,7 +1031,7 @@ bool zones_empty()
   if(g.n_zones == 0) return true;
   std::vector<uint32_t> v(g.n_zones);
   for(int p = 0; p < 2; ++p)
-    for(uint32_t* src : {g.d_land_n[p], g.d_carry_n[p]})
+    for(const uint32_t* src : {g.d_land_n[p].get(), g.d_carry_n[p].get()})
     {
       if(hipMemcpy(v.data(), src, g.n_zones * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
         return false;
@@ -1099,70 +1105,67 @@ int relayout_zones(bool geometry)
     off[z] = total;
     total += (cap[z] + 15u) & ~15u;          // keep every zone 256-B aligned
   }
-  const size_t bytes = std::max<uint64_t>(total, 16) * sizeof(ZRec);
-  uint64_t* d_off = nullptr;
-  uint32_t* d_cap = nullptr;
-  HIPCK(hipMalloc(&d_off, std::max<size_t>(nz, 1) * sizeof(uint64_t)));
-  HIPCK(hipMalloc(&d_cap, std::max<size_t>(nz, 1) * sizeof(uint32_t)));
+  // The new layout is built in local buffers and swapped in after the last
+  // call that can fail: a failure leaves the old layout as it was.
+  const size_t recs = std::max<uint64_t>(total, 16), nzn = std::max<size_t>(nz, 1);
+  DevBuf<uint64_t> d_off;
+  DevBuf<uint32_t> d_cap, ln[2], cn[2], mo;
+  DevBuf<ZRec> land[2], carry[2], S;
+  DevBuf<ORec> O;
+  HIPCK(d_off.alloc(nzn));
+  HIPCK(d_cap.alloc(nzn));
   HIPCK(hipMemcpyAsync(d_off, off.data(), nz * sizeof(uint64_t), hipMemcpyHostToDevice, g.stream));
   HIPCK(hipMemcpyAsync(d_cap, cap.data(), nz * sizeof(uint32_t), hipMemcpyHostToDevice, g.stream));
   for(int p = 0; p < 2; ++p)
   {
-    ZRec *land = nullptr, *carry = nullptr;
-    uint32_t *ln = nullptr, *cn = nullptr;
-    HIPCK(hipMalloc(&land, bytes));
-    HIPCK(hipMalloc(&carry, bytes));
-    HIPCK(hipMalloc(&ln, std::max<size_t>(nz, 1) * sizeof(uint32_t)));
-    HIPCK(hipMalloc(&cn, std::max<size_t>(nz, 1) * sizeof(uint32_t)));
-    HIPCK(hipMemsetAsync(ln, 0, std::max<size_t>(nz, 1) * sizeof(uint32_t), g.stream));
-    HIPCK(hipMemsetAsync(cn, 0, std::max<size_t>(nz, 1) * sizeof(uint32_t), g.stream));
+    HIPCK(land[p].alloc(recs));
+    HIPCK(carry[p].alloc(recs));
+    HIPCK(ln[p].alloc(nzn));
+    HIPCK(cn[p].alloc(nzn));
+    HIPCK(hipMemsetAsync(ln[p], 0, nzn * sizeof(uint32_t), g.stream));
+    HIPCK(hipMemsetAsync(cn[p], 0, nzn * sizeof(uint32_t), g.stream));
     if(g.n_zones && !fresh)
     {
       hipLaunchKernelGGL(k_zone_copy, dim3(g.n_zones), dim3(kBlock), 0, g.stream,
-        (const ZRec*)g.d_land[p], g.d_zoff, g.d_zcap, land, (const uint64_t*)d_off);
+        (const ZRec*)g.d_land[p], g.d_zoff, g.d_zcap, land[p], (const uint64_t*)d_off);
       hipLaunchKernelGGL(k_zone_copy, dim3(g.n_zones), dim3(kBlock), 0, g.stream,
-        (const ZRec*)g.d_carry[p], g.d_zoff, g.d_zcap, carry, (const uint64_t*)d_off);
+        (const ZRec*)g.d_carry[p], g.d_zoff, g.d_zcap, carry[p], (const uint64_t*)d_off);
       HIPCK(hipGetLastError());
-      HIPCK(hipMemcpyAsync(ln, g.d_land_n[p], g.n_zones * sizeof(uint32_t),
+      HIPCK(hipMemcpyAsync(ln[p], g.d_land_n[p], g.n_zones * sizeof(uint32_t),
         hipMemcpyDeviceToDevice, g.stream));
-      HIPCK(hipMemcpyAsync(cn, g.d_carry_n[p], g.n_zones * sizeof(uint32_t),
+      HIPCK(hipMemcpyAsync(cn[p], g.d_carry_n[p], g.n_zones * sizeof(uint32_t),
         hipMemcpyDeviceToDevice, g.stream));
     }
     HIPCK(hipStreamSynchronize(g.stream));
-    if(g.d_land[p]) HIPCK(hipFree(g.d_land[p]));
-    if(g.d_carry[p]) HIPCK(hipFree(g.d_carry[p]));
-    if(g.d_land_n[p]) HIPCK(hipFree(g.d_land_n[p]));
-    if(g.d_carry_n[p]) HIPCK(hipFree(g.d_carry_n[p]));
-    g.d_land[p] = land; g.d_carry[p] = carry; g.d_land_n[p] = ln; g.d_carry_n[p] = cn;
   }
-  if(g.d_S) HIPCK(hipFree(g.d_S));
-  if(g.d_O) HIPCK(hipFree(g.d_O));
-  if(g.d_zoff) HIPCK(hipFree(g.d_zoff));
-  if(g.d_zcap) HIPCK(hipFree(g.d_zcap));
-  HIPCK(hipMalloc(&g.d_S, 3 * bytes));     // 2 x: records of a zone; 1 x: sort scratch
-  HIPCK(hipMalloc(&g.d_O, std::max<uint64_t>(total, 16) * sizeof(ORec)));
-  g.d_zoff = d_off;
-  g.d_zcap = d_cap;
-  g.zone_records = total;
-  g.n_zones = nz;
-  g.zcap_host = cap;
+  HIPCK(S.alloc(3 * recs));                // 2 x: records of a zone; 1 x: sort scratch
+  HIPCK(O.alloc(recs));
   // the receiver each muted actor waits on, one word per local slot
   const uint64_t slots = (uint64_t)nz * za;
-  if(slots > g.muted_on_cap)
+  if(slots > g.d_muted_on.size())
   {
-    uint32_t* mo = nullptr;
-    HIPCK(hipMalloc(&mo, slots * sizeof(uint32_t)));
+    HIPCK(mo.alloc(slots));
     HIPCK(hipMemsetAsync(mo, 0, slots * sizeof(uint32_t), g.stream));
     if(g.d_muted_on)
     {
-      HIPCK(hipMemcpyAsync(mo, g.d_muted_on, g.muted_on_cap * sizeof(uint32_t),
+      HIPCK(hipMemcpyAsync(mo, g.d_muted_on, g.d_muted_on.size() * sizeof(uint32_t),
         hipMemcpyDeviceToDevice, g.stream));
       HIPCK(hipStreamSynchronize(g.stream));
-      HIPCK(hipFree(g.d_muted_on));
     }
-    g.d_muted_on = mo;
-    g.muted_on_cap = slots;
+    g.d_muted_on.swap(mo);
   }
+  for(int p = 0; p < 2; ++p)
+  {
+    g.d_land[p].swap(land[p]); g.d_carry[p].swap(carry[p]);
+    g.d_land_n[p].swap(ln[p]); g.d_carry_n[p].swap(cn[p]);
+  }
+  g.d_S.swap(S);
+  g.d_O.swap(O);
+  g.d_zoff.swap(d_off);
+  g.d_zcap.swap(d_cap);
+  g.zone_records = total;
+  g.n_zones = nz;
+  g.zcap_host = cap;
   // (the spill lists are re-sized by the callers, once nothing is left in
   // them: fixup_spill relays the zones while its spilled records wait there)
   return 0;
@@ -1558,9 +1561,8 @@ __global__ void __launch_bounds__(kBlock) k_xspill_place(uint32_t n)
 
 int alloc_xspill(uint32_t cap)
 {
-  if(g.d_xspill) HIPCK(hipFree(g.d_xspill));
-  g.d_xspill = nullptr;
-  HIPCK(hipMalloc(&g.d_xspill, (size_t)cap * sizeof(XSpillRec)));
+  g.xspill_cap = 0;
+  HIPCK(g.d_xspill.alloc(cap));
   g.xspill_cap = cap;
   return 0;
 }
@@ -1579,13 +1581,12 @@ int exchange_room(uint64_t max_send, uint64_t total_recv, uint64_t xs)
   {
     uint64_t cap = std::max<uint64_t>(2ull * g.xcap, max_send + max_send / 2);
     cap = std::min<uint64_t>((cap + 63) & ~63ull, 0x40000000ull);
-    XRec* nx = nullptr;
-    HIPCK(hipMalloc(&nx, (size_t)R() * cap * sizeof(XRec)));
+    DevBuf<XRec> nx;
+    HIPCK(nx.alloc((size_t)R() * cap));
     HIPCK(hipMemcpy2DAsync(nx, cap * sizeof(XRec), g.d_xout, (size_t)g.xcap * sizeof(XRec),
       (size_t)g.xcap * sizeof(XRec), R(), hipMemcpyDeviceToDevice, g.stream));
     HIPCK(hipStreamSynchronize(g.stream));
-    HIPCK(hipFree(g.d_xout));
-    g.d_xout = nx;
+    g.d_xout = std::move(nx);
     g.xcap = (uint32_t)cap;
     const int rc = upload_types();
     if(rc) return rc;
@@ -1610,14 +1611,11 @@ int exchange_room(uint64_t max_send, uint64_t total_recv, uint64_t xs)
       if(rc2) return rc2;
     }
   }
-  if(total_recv > g.xin_cap)
+  if(total_recv > g.d_xin.size())
   {
-    const uint64_t cap = std::max<uint64_t>(2ull * g.xin_cap, total_recv + total_recv / 2);
+    const uint64_t cap = std::max<uint64_t>(2ull * g.d_xin.size(), total_recv + total_recv / 2);
     HIPCK(hipStreamSynchronize(g.stream));
-    HIPCK(hipFree(g.d_xin));
-    g.d_xin = nullptr;
-    HIPCK(hipMalloc(&g.d_xin, cap * sizeof(XRec)));
-    g.xin_cap = cap;
+    HIPCK(g.d_xin.alloc(cap));
   }
   return 0;
 }
@@ -1636,22 +1634,8 @@ enum XcType { XC_U8 = 0, XC_U32 = 1, XC_U64 = 2 };
 
 int stage_room(uint64_t sbytes, uint64_t rbytes)
 {
-  if(sbytes > g.h_sbuf_cap)
-  {
-    if(g.h_sbuf) HIPCK(hipHostFree(g.h_sbuf));
-    g.h_sbuf = nullptr;
-    const uint64_t c = std::max<uint64_t>(sbytes, 2 * g.h_sbuf_cap);
-    HIPCK(hipHostMalloc(&g.h_sbuf, c, hipHostMallocDefault));
-    g.h_sbuf_cap = c;
-  }
-  if(rbytes > g.h_rbuf_cap)
-  {
-    if(g.h_rbuf) HIPCK(hipHostFree(g.h_rbuf));
-    g.h_rbuf = nullptr;
-    const uint64_t c = std::max<uint64_t>(rbytes, 2 * g.h_rbuf_cap);
-    HIPCK(hipHostMalloc(&g.h_rbuf, c, hipHostMallocDefault));
-    g.h_rbuf_cap = c;
-  }
+  if(sbytes > g.h_sbuf.size()) HIPCK(g.h_sbuf.alloc(std::max<uint64_t>(sbytes, 2 * g.h_sbuf.size())));
+  if(rbytes > g.h_rbuf.size()) HIPCK(g.h_rbuf.alloc(std::max<uint64_t>(rbytes, 2 * g.h_rbuf.size())));
   return 0;
 }
 
@@ -1661,7 +1645,7 @@ int stage_room(uint64_t sbytes, uint64_t rbytes)
 int xc_allreduce_sum(const void* d_in, void* d_out, uint64_t count, XcType t)
 {
   if(count == 0) return 0;
-  if(!g.xp_ar)
+  if(!gp.xp_ar)
   {
     const ncclDataType_t nt = t == XC_U8 ? ncclUint8 : t == XC_U32 ? ncclUint32 : ncclUint64;
     NCCLCK(ncclAllReduce(d_in, d_out, count, nt, ncclSum, g.comm, g.stream));
@@ -1672,18 +1656,18 @@ int xc_allreduce_sum(const void* d_in, void* d_out, uint64_t count, XcType t)
   const uint64_t words = t == XC_U64 ? count : t == XC_U8 ? (bytes + 7) / 8 : count;
   int rc = stage_room(words * 8, bytes);
   if(rc) return rc;
-  uint64_t* w = reinterpret_cast<uint64_t*>(g.h_sbuf);
+  uint64_t* w = reinterpret_cast<uint64_t*>(g.h_sbuf.get());
   if(t == XC_U8) memset(w, 0, words * 8);
   HIPCK(hipMemcpyAsync(t == XC_U32 ? g.h_rbuf : g.h_sbuf, d_in, bytes, hipMemcpyDeviceToHost,
     g.stream));
   HIPCK(hipStreamSynchronize(g.stream));
   if(t == XC_U32)
-    for(uint64_t i = 0; i < count; ++i) w[i] = reinterpret_cast<const uint32_t*>(g.h_rbuf)[i];
-  if(g.xp_ar(g.xp_ctx, w, words) != 0) return GPU_ACTOR_ECOMM;
+    for(uint64_t i = 0; i < count; ++i) w[i] = reinterpret_cast<const uint32_t*>(g.h_rbuf.get())[i];
+  if(gp.xp_ar(gp.xp_ctx, w, words) != 0) return GPU_ACTOR_ECOMM;
   if(t == XC_U32)
   {
     for(uint64_t i = 0; i < count; ++i)
-      reinterpret_cast<uint32_t*>(g.h_rbuf)[i] = (uint32_t)std::min<uint64_t>(w[i], 0xFFFFFFFFull);
+      reinterpret_cast<uint32_t*>(g.h_rbuf.get())[i] = (uint32_t)std::min<uint64_t>(w[i], 0xFFFFFFFFull);
     HIPCK(hipMemcpyAsync(d_out, g.h_rbuf, bytes, hipMemcpyHostToDevice, g.stream));
   }
   else
@@ -1696,7 +1680,7 @@ int xc_allreduce_sum(const void* d_in, void* d_out, uint64_t count, XcType t)
 int xc_alltoall_u64(const unsigned long long* d_send, unsigned long long* d_recv)
 {
   const uint32_t n = R();
-  if(!g.xp_a2a)
+  if(!gp.xp_a2a)
   {
     NCCLCK(ncclAllToAll(d_send, d_recv, 1, ncclUint64, g.comm, g.stream));
     return 0;
@@ -1706,7 +1690,7 @@ int xc_alltoall_u64(const unsigned long long* d_send, unsigned long long* d_recv
   HIPCK(hipMemcpyAsync(g.h_sbuf, d_send, n * 8, hipMemcpyDeviceToHost, g.stream));
   HIPCK(hipStreamSynchronize(g.stream));
   std::vector<uint64_t> b8(n, 8);
-  if(g.xp_a2a(g.xp_ctx, g.h_sbuf, b8.data(), g.h_rbuf, b8.data()) != 0) return GPU_ACTOR_ECOMM;
+  if(gp.xp_a2a(gp.xp_ctx, g.h_sbuf, b8.data(), g.h_rbuf, b8.data()) != 0) return GPU_ACTOR_ECOMM;
   HIPCK(hipMemcpyAsync(d_recv, g.h_rbuf, n * 8, hipMemcpyHostToDevice, g.stream));
   HIPCK(hipStreamSynchronize(g.stream));
   return 0;
@@ -1716,7 +1700,7 @@ int xc_alltoall_u64(const unsigned long long* d_send, unsigned long long* d_recv
 int xc_allgather_u64(const unsigned long long* d_in, unsigned long long* d_out)
 {
   const uint32_t n = R();
-  if(!g.xp_a2a)
+  if(!gp.xp_a2a)
   {
     NCCLCK(ncclAllGather(d_in, d_out, 1, ncclUint64, g.comm, g.stream));
     return 0;
@@ -1725,10 +1709,10 @@ int xc_allgather_u64(const unsigned long long* d_in, unsigned long long* d_out)
   if(rc) return rc;
   HIPCK(hipMemcpyAsync(g.h_sbuf, d_in, 8, hipMemcpyDeviceToHost, g.stream));
   HIPCK(hipStreamSynchronize(g.stream));
-  uint64_t* sw = reinterpret_cast<uint64_t*>(g.h_sbuf);
+  uint64_t* sw = reinterpret_cast<uint64_t*>(g.h_sbuf.get());
   for(uint32_t p = 1; p < n; ++p) sw[p] = sw[0];
   std::vector<uint64_t> b8(n, 8);
-  if(g.xp_a2a(g.xp_ctx, g.h_sbuf, b8.data(), g.h_rbuf, b8.data()) != 0) return GPU_ACTOR_ECOMM;
+  if(gp.xp_a2a(gp.xp_ctx, g.h_sbuf, b8.data(), g.h_rbuf, b8.data()) != 0) return GPU_ACTOR_ECOMM;
   HIPCK(hipMemcpyAsync(d_out, g.h_rbuf, n * 8, hipMemcpyHostToDevice, g.stream));
   HIPCK(hipStreamSynchronize(g.stream));
   return 0;
@@ -1745,7 +1729,7 @@ struct XcPeer {
 int xc_sendrecv(const std::vector<XcPeer>& pp)
 {
   const uint32_t n = R();
-  if(!g.xp_a2a)
+  if(!gp.xp_a2a)
   {
     NCCLCK(ncclGroupStart());
     for(uint32_t p = 0; p < n; ++p)
@@ -1776,7 +1760,7 @@ int xc_sendrecv(const std::vector<XcPeer>& pp)
     off += sb[p];
   }
   HIPCK(hipStreamSynchronize(g.stream));
-  if(g.xp_a2a(g.xp_ctx, g.h_sbuf, sb.data(), g.h_rbuf, rb.data()) != 0) return GPU_ACTOR_ECOMM;
+  if(gp.xp_a2a(gp.xp_ctx, g.h_sbuf, sb.data(), g.h_rbuf, rb.data()) != 0) return GPU_ACTOR_ECOMM;
   off = 0;
   for(uint32_t p = 0; p < n; ++p)
   {
@@ -1878,14 +1862,13 @@ int peer_room(uint64_t max_send, uint64_t xs)
   }
   if(cap > g.xcap)
   {
-    XRec* nx = nullptr;
-    HIPCK(hipMalloc(&nx, (size_t)n * cap * sizeof(XRec)));
+    DevBuf<XRec> nx;
+    HIPCK(nx.alloc((size_t)n * cap));
     HIPCK(hipMemcpy2DAsync(nx, cap * sizeof(XRec), g.d_pin, (size_t)g.xcap * sizeof(XRec),
       (size_t)g.xcap * sizeof(XRec), n, hipMemcpyDeviceToDevice, g.stream));
     HIPCK(hipStreamSynchronize(g.stream));
     peer_close();
-    HIPCK(hipFree(g.d_pin));
-    g.d_pin = nx;
+    g.d_pin = std::move(nx);
     g.xcap = (uint32_t)cap;
     rc = peer_open();
     if(rc) return rc;
@@ -1953,7 +1936,7 @@ int exchange_step(uint32_t step_sidx)
     hipMemcpyDeviceToHost, g.stream));
   HIPCK(hipMemcpyAsync(g.h_xc + 2 * n + 1, g.d_xspill_n, sizeof(unsigned int),
     hipMemcpyDeviceToHost, g.stream));
-  HIPCK(hipMemcpyAsync(g.h_sstat, g.d_sstat, sizeof(Engine::SpillStat), hipMemcpyDeviceToHost,
+  HIPCK(hipMemcpyAsync(g.h_sstat, g.d_sstat, sizeof(SpillStat), hipMemcpyDeviceToHost,
     g.stream));
   HIPCK(hipStreamSynchronize(g.stream));
   tcount = (unsigned int)(g.h_xc[2 * n] & 0xFFFFFFFFull);
@@ -2063,7 +2046,7 @@ size_t step_dyn_bytes(const StepEntry& se, uint64_t nb)
 // every kernel of the entry (hipFuncGetAttributes) + the dynamic part.
 bool step_fits(const StepEntry& se, uint64_t nb)
 {
-  static std::map<step_kernel_t, size_t> cache;     // (callers hold g.mu)
+  static std::map<step_kernel_t, size_t> cache;     // (callers hold gp.mu)
   size_t st = 0;
   for(step_kernel_t k : {se.kernel, se.plan, se.rest, se.fused})
   {
@@ -2089,6 +2072,12 @@ bool step_fits(const StepEntry& se, uint64_t nb)
 // messages of the actors it owns (owner = id % n_ranks): the ids equal a
 // single rank's (pony_create inside behaviours is rank-agnostic,
 // actor.c:688-734).
+// hipcub's scratch for the sorts of spawn_process and host_collect
+hipError_t sort_room(size_t bytes)
+{
+  return bytes > g.d_sort_tmp.size() ? g.d_sort_tmp.alloc(bytes) : hipSuccess;
+}
+
 int spawn_process(uint32_t cur)
 {
   unsigned int n = 0;
@@ -2106,13 +2095,12 @@ int spawn_process(uint32_t cur)
       unsigned long long* dc = g.d_xc + 2 * nr;     // scratch words of the counts block
       const unsigned long long mine = n;
       HIPCK(hipMemcpyAsync(dc, &mine, sizeof(mine), hipMemcpyHostToDevice, g.stream));
-      unsigned long long* dall = nullptr;
-      HIPCK(hipMalloc(&dall, nr * sizeof(unsigned long long)));
+      DevBuf<unsigned long long> dall;
+      HIPCK(dall.alloc(nr));
       int rc = xc_allgather_u64(dc, dall);
-      if(rc) { (void)hipFree(dall); return rc; }
+      if(rc) return rc;
       HIPCK(hipMemcpyAsync(cnt.data(), dall, nr * sizeof(uint64_t), hipMemcpyDeviceToHost, g.stream));
       HIPCK(hipStreamSynchronize(g.stream));
-      HIPCK(hipFree(dall));
     }
     // every rank's whole list, in rank order (each list holds at most
     // spawn_cap records; past that its own device counted the drops): the
@@ -2163,16 +2151,12 @@ int spawn_process(uint32_t cur)
   }
   if(total == 0) return 0;
   size_t need = 0;
-  HIPCK(hipcub::DeviceRadixSort::SortPairs(nullptr, need, key, g.d_skey[1], arg,
-    g.d_sarg[1], (int)total, 0, 56, g.stream));
-  if(need > g.sort_tmp_bytes)
-  {
-    if(g.d_sort_tmp) HIPCK(hipFree(g.d_sort_tmp));
-    HIPCK(hipMalloc(&g.d_sort_tmp, need));
-    g.sort_tmp_bytes = need;
-  }
-  HIPCK(hipcub::DeviceRadixSort::SortPairs(g.d_sort_tmp, need, key, g.d_skey[1],
-    arg, g.d_sarg[1], (int)total, 0, 56, g.stream));
+  uint64_t *key_out = g.d_skey[1], *arg_out = g.d_sarg[1];
+  HIPCK(hipcub::DeviceRadixSort::SortPairs(nullptr, need, key, key_out, arg, arg_out, (int)total, 0, 56,
+    g.stream));
+  HIPCK(sort_room(need));
+  HIPCK(hipcub::DeviceRadixSort::SortPairs(g.d_sort_tmp, need, key, key_out, arg, arg_out, (int)total, 0,
+    56, g.stream));
   HIPCK(hipMemsetAsync(g.d_tstart, 0xFF, GPU_ACTOR_MAX_TYPES * sizeof(uint32_t), g.stream));
   HIPCK(hipMemsetAsync(g.d_tcnt, 0, GPU_ACTOR_MAX_TYPES * sizeof(uint32_t), g.stream));
   hipLaunchKernelGGL(k_spawn_scan, dim3(blocks_for(total)), dim3(kBlock), 0, g.stream,
@@ -2192,48 +2176,28 @@ int spawn_process(uint32_t cur)
 // sum to at least the reserve (send_host fills a full segment's neighbours, so
 // nothing is lost before every segment is full; a collection keeps at most
 // the reserve). Called with nothing listed (between collections).
-void host_free()
-{
-  if(g.d_host_key) (void)hipFree(g.d_host_key);
-  if(g.d_host_kc) (void)hipFree(g.d_host_kc);
-  if(g.d_host_ks) (void)hipFree(g.d_host_ks);
-  if(g.d_host_ic) (void)hipFree(g.d_host_ic);
-  if(g.d_host_is) (void)hipFree(g.d_host_is);
-  if(g.d_host_rec) (void)hipFree(g.d_host_rec);
-  if(g.d_host_out) (void)hipFree(g.d_host_out);
-  if(g.h_host_out) (void)hipHostFree(g.h_host_out);
-  g.d_host_key = g.d_host_kc = g.d_host_ks = nullptr;
-  g.d_host_ic = g.d_host_is = nullptr;
-  g.d_host_rec = nullptr; g.d_host_out = nullptr; g.h_host_out = nullptr;
-  g.host_seg = 0;
-}
-
 int host_alloc()
 {
   HIPCK(hipStreamSynchronize(g.stream));        // no step still lists into the old segments
-  host_free();
+  g.hl = {};
+  g.host_seg = 0;
   if(!g.d_host_n)
   {
-    HIPCK(hipMalloc(&g.d_host_n, kHostShards * sizeof(unsigned int)));
+    HIPCK(g.d_host_n.alloc(kHostShards));
     HIPCK(hipMemsetAsync(g.d_host_n, 0, kHostShards * sizeof(unsigned int), g.stream));
-    HIPCK(hipHostMalloc(&g.h_host_n, kHostShards * sizeof(unsigned int), hipHostMallocDefault));
-    HIPCK(hipMalloc(&g.d_host_step, sizeof(uint64_t)));
+    HIPCK(g.h_host_n.alloc(kHostShards));
+    HIPCK(g.d_host_step.alloc(1));
     HIPCK(hipMemsetAsync(g.d_host_step, 0, sizeof(uint64_t), g.stream));
   }
   const uint64_t n = g.host_reserve;
   const uint32_t seg = (uint32_t)((n + kHostShards - 1) / kHostShards);
   const size_t room = (size_t)seg * kHostShards;
   auto ck = [](hipError_t e) { if(e != hipSuccess) (void)hipGetLastError(); return e == hipSuccess; };
-  if(!ck(hipMalloc(&g.d_host_key, room * sizeof(uint64_t))) ||
-     !ck(hipMalloc(&g.d_host_kc, room * sizeof(uint64_t))) ||
-     !ck(hipMalloc(&g.d_host_ks, room * sizeof(uint64_t))) ||
-     !ck(hipMalloc(&g.d_host_ic, room * sizeof(uint32_t))) ||
-     !ck(hipMalloc(&g.d_host_is, room * sizeof(uint32_t))) ||
-     !ck(hipMalloc(&g.d_host_rec, room * sizeof(uint4))) ||
-     !ck(hipMalloc(&g.d_host_out, n * sizeof(gpu_host_msg_t))) ||
-     !ck(hipHostMalloc(&g.h_host_out, n * sizeof(gpu_host_msg_t), hipHostMallocDefault)))
+  if(!ck(g.hl.d_host_key.alloc(room)) || !ck(g.hl.d_host_kc.alloc(room)) || !ck(g.hl.d_host_ks.alloc(room)) ||
+     !ck(g.hl.d_host_ic.alloc(room)) || !ck(g.hl.d_host_is.alloc(room)) || !ck(g.hl.d_host_rec.alloc(room)) ||
+     !ck(g.hl.d_host_out.alloc(n)) || !ck(g.hl.h_host_out.alloc(n)))
   {
-    host_free();
+    g.hl = {};                                  // no room: none of the lists is kept
     return GPU_ACTOR_ENOMEM;
   }
   g.host_seg = seg;
@@ -2278,43 +2242,37 @@ int host_collect()
   if(total == 0) return 0;
   const uint32_t n = (uint32_t)total;
   hipLaunchKernelGGL(k_host_compact, dim3(blocks_for(n)), dim3(kBlock), 0, g.stream,
-    (const uint64_t*)g.d_host_key, o, g.host_seg, g.d_host_kc, g.d_host_ic);
+    (const uint64_t*)g.hl.d_host_key, o, g.host_seg, g.hl.d_host_kc, g.hl.d_host_ic);
   HIPCK(hipGetLastError());
   int end_bit = (int)g.host_kshift;
   while(end_bit < 64 && (uint64_t)steps > (1ull << (end_bit - (int)g.host_kshift))) ++end_bit;
   size_t need = 0;
-  HIPCK(hipcub::DeviceRadixSort::SortPairs(nullptr, need, g.d_host_kc, g.d_host_ks, g.d_host_ic,
-    g.d_host_is, (int)n, 0, end_bit, g.stream));
-  if(need > g.sort_tmp_bytes)
-  {
-    if(g.d_sort_tmp) HIPCK(hipFree(g.d_sort_tmp));
-    g.d_sort_tmp = nullptr;
-    g.sort_tmp_bytes = 0;
-    HIPCK(hipMalloc(&g.d_sort_tmp, need));
-    g.sort_tmp_bytes = need;
-  }
-  HIPCK(hipcub::DeviceRadixSort::SortPairs(g.d_sort_tmp, need, g.d_host_kc, g.d_host_ks, g.d_host_ic,
-    g.d_host_is, (int)n, 0, end_bit, g.stream));
+  uint64_t *kc = g.hl.d_host_kc, *ks = g.hl.d_host_ks;
+  uint32_t *ic = g.hl.d_host_ic, *is = g.hl.d_host_is;
+  HIPCK(hipcub::DeviceRadixSort::SortPairs(nullptr, need, kc, ks, ic, is, (int)n, 0, end_bit, g.stream));
+  HIPCK(sort_room(need));
+  HIPCK(hipcub::DeviceRadixSort::SortPairs(g.d_sort_tmp, need, kc, ks, ic, is, (int)n, 0, end_bit,
+    g.stream));
   const uint32_t keep = (uint32_t)std::min<uint64_t>(n, g.host_reserve);
   hipLaunchKernelGGL(k_host_gather, dim3(blocks_for(keep)), dim3(kBlock), 0, g.stream,
-    (const uint64_t*)g.d_host_ks, (const uint32_t*)g.d_host_is, (const uint4*)g.d_host_rec,
-    g.d_host_out, keep, (uint64_t)g.host_base, g.host_kshift);
+    (const uint64_t*)g.hl.d_host_ks, (const uint32_t*)g.hl.d_host_is, (const uint4*)g.hl.d_host_rec,
+    g.hl.d_host_out, keep, (uint64_t)g.host_base, g.host_kshift);
   if(n > keep)
   {
     hipLaunchKernelGGL(k_host_lost, dim3(1), dim3(1), 0, g.stream, (unsigned long long)(n - keep));
     g.dev_epoch++;
   }
   HIPCK(hipGetLastError());
-  HIPCK(hipMemcpyAsync(g.h_host_out, g.d_host_out, (size_t)keep * sizeof(gpu_host_msg_t),
+  HIPCK(hipMemcpyAsync(g.hl.h_host_out, g.hl.d_host_out, (size_t)keep * sizeof(gpu_host_msg_t),
     hipMemcpyDeviceToHost, g.stream));
   HIPCK(hipMemsetAsync(g.d_host_n, 0, kHostShards * sizeof(unsigned int), g.stream));
   HIPCK(hipStreamSynchronize(g.stream));
   if(g.host_fn)
-    g.host_fn(g.host_ctx, g.h_host_out, keep);
+    g.host_fn(g.host_ctx, g.hl.h_host_out, keep);
   else
   {
     if(g.hostq_head == g.hostq.size()) { g.hostq.clear(); g.hostq_head = 0; }
-    try { g.hostq.insert(g.hostq.end(), g.h_host_out, g.h_host_out + keep); }
+    try { g.hostq.insert(g.hostq.end(), g.hl.h_host_out.get(), g.hl.h_host_out + keep); }
     catch(...) { return GPU_ACTOR_ENOMEM; }
   }
   return 0;
@@ -2510,15 +2468,11 @@ int gups_gather_apply(hipEvent_t e1)
   const uint64_t mine = cnt[rank()];
   g.gups_out_total += mine;
   g.gups_in_total += total - mine;
-  if(total > g.gups_all_cap)
+  if(total > g.d_gups_all.size())
   {
-    const uint64_t cap = std::max<uint64_t>({2ull * g.gups_all_cap, total + total / 2, 1ull << 16});
+    const uint64_t cap = std::max<uint64_t>({2ull * g.d_gups_all.size(), total + total / 2, 1ull << 16});
     HIPCK(hipStreamSynchronize(g.stream));      // no k_gups_apply_ranks still reads the old one
-    if(g.d_gups_all) HIPCK(hipFree(g.d_gups_all));
-    g.d_gups_all = nullptr;
-    g.gups_all_cap = 0;
-    HIPCK(hipMalloc(&g.d_gups_all, cap * sizeof(uint64_t)));
-    g.gups_all_cap = cap;
+    HIPCK(g.d_gups_all.alloc(cap));
   }
   bool launched = false;
   if(total)
@@ -2658,101 +2612,23 @@ int ensure_events(size_t n)
   return 0;
 }
 
-void free_all()
+// The end of a session (gpu_actor_shutdown, a failed gpu_actor_init): the
+// run-time compiled module, the peers' mapped inboxes, then the session's
+// value — every buffer frees itself — replaced by a fresh one; the events, the
+// communicator and the stream go last.
+void session_end()
 {
+  if(g.stream) (void)hipStreamSynchronize(g.stream);
   jit::unload(g.jit);
-  g.jit_set = g.jit_failed = 0;
-  g.jit_builds = 0;
-  g.jit_used = g.consts_host = false;
-  if(g.d_gups_list) (void)hipFree(g.d_gups_list);
-  if(g.d_gups_n) (void)hipFree(g.d_gups_n);
-  if(g.d_gups_jump) (void)hipFree(g.d_gups_jump);
-  if(g.d_gups_stat) (void)hipFree(g.d_gups_stat);
-  if(g.d_gups_send) (void)hipFree(g.d_gups_send);
-  if(g.d_gups_all) (void)hipFree(g.d_gups_all);
-  g.d_gups_send = nullptr; g.d_gups_all = nullptr;
-  g.gups_all_cap = 0; g.gups_parts = 0; g.gups_in_total = g.gups_out_total = 0;
-  g.d_gups_list = nullptr; g.d_gups_n = nullptr; g.d_gups_jump = nullptr; g.d_gups_stat = nullptr;
-  memset(g.gups_jump_host, 0, sizeof(g.gups_jump_host));
-  g.gups_cap = 0;
-  g.gups_type = -1;
-  for(auto& t : g.types)
-  {
-    if(t.d_state) (void)hipFree(t.d_state);
-    if(t.d_prog) (void)hipFree(t.d_prog);
-  }
-  for(int p = 0; p < 2; ++p)
-  {
-    if(g.d_land[p]) (void)hipFree(g.d_land[p]);
-    if(g.d_carry[p]) (void)hipFree(g.d_carry[p]);
-    if(g.d_land_n[p]) (void)hipFree(g.d_land_n[p]);
-    if(g.d_carry_n[p]) (void)hipFree(g.d_carry_n[p]);
-  }
-  if(g.d_S) (void)hipFree(g.d_S);
-  if(g.d_O) (void)hipFree(g.d_O);
-  if(g.d_zoff) (void)hipFree(g.d_zoff);
-  if(g.d_zcap) (void)hipFree(g.d_zcap);
-  for(int p = 0; p < 2; ++p)
-  {
-    if(g.d_skey[p]) (void)hipFree(g.d_skey[p]);
-    if(g.d_sarg[p]) (void)hipFree(g.d_sarg[p]);
-  }
-  if(g.d_spawn_n) (void)hipFree(g.d_spawn_n);
-  if(g.d_tstart) (void)hipFree(g.d_tstart);
-  if(g.d_tcnt) (void)hipFree(g.d_tcnt);
-  if(g.d_live) (void)hipFree(g.d_live);
-  if(g.d_ctl) (void)hipFree(g.d_ctl);
-  for(int p = 0; p < 2; ++p)
-    if(g.d_spill[p]) (void)hipFree(g.d_spill[p]);
-  if(g.d_sstat) (void)hipFree(g.d_sstat);
-  if(g.h_sstat) (void)hipHostFree(g.h_sstat);
-  if(g.d_need) (void)hipFree(g.d_need);
-  for(int p = 0; p < 2; ++p)
-  {
-    if(g.d_trig[p]) (void)hipFree(g.d_trig[p]);
-    if(g.d_trig_own[p]) (void)hipFree(g.d_trig_own[p]);
-    if(g.d_ztrig[p]) (void)hipFree(g.d_ztrig[p]);
-  }
-  if(g.d_zplan) (void)hipFree(g.d_zplan);
-  if(g.d_muted_on) (void)hipFree(g.d_muted_on);
-  if(g.d_trig_n) (void)hipFree(g.d_trig_n);
-  if(g.d_bigc) (void)hipFree(g.d_bigc);
-  if(g.d_bigc_n) (void)hipFree(g.d_bigc_n);
-  if(g.h_ctl) (void)hipHostFree(g.h_ctl);
-  if(g.d_sort_tmp) (void)hipFree(g.d_sort_tmp);
-  if(g.d_stats) (void)hipFree(g.d_stats);
-  if(g.d_pend) (void)hipFree(g.d_pend);
-  if(g.d_pend_sh) (void)hipFree(g.d_pend_sh);
-  if(g.d_stats_sh) (void)hipFree(g.d_stats_sh);
-  if(g.d_hot) (void)hipFree(g.d_hot);
-  if(g.d_dbg) (void)hipFree(g.d_dbg);
-  if(g.h_msgs) (void)hipHostFree(g.h_msgs);
-  if(g.d_msgs) (void)hipFree(g.d_msgs);
-  if(g.d_xout) (void)hipFree(g.d_xout);
-  if(g.d_xin) (void)hipFree(g.d_xin);
   peer_close();
-  if(g.d_pin) (void)hipFree(g.d_pin);
-  if(g.d_hx) (void)hipFree(g.d_hx);
-  if(g.d_xspill) (void)hipFree(g.d_xspill);
-  if(g.d_xspill_n) (void)hipFree(g.d_xspill_n);
-  if(g.d_xc) (void)hipFree(g.d_xc);
-  if(g.h_xc) (void)hipHostFree(g.h_xc);
-  if(g.d_spill_flag) (void)hipFree(g.d_spill_flag);
-  if(g.h_sbuf) (void)hipHostFree(g.h_sbuf);
-  if(g.h_rbuf) (void)hipHostFree(g.h_rbuf);
-  host_free();
-  if(g.d_host_n) (void)hipFree(g.d_host_n);
-  if(g.h_host_n) (void)hipHostFree(g.h_host_n);
-  if(g.d_host_step) (void)hipFree(g.d_host_step);
-  g.d_host_n = nullptr; g.h_host_n = nullptr; g.d_host_step = nullptr;
-  g.host_ports = g.host_dirty = g.host_defer = false;
-  g.host_base = 0;
-  g.host_reserve = GPU_ACTOR_HOST_RESERVE_DEFAULT;
-  g.hostq.clear(); g.hostq_head = 0;
-  g.host_fn = nullptr; g.host_ctx = nullptr;
-  for(hipEvent_t e : g.ev) (void)hipEventDestroy(e);
-  if(g.comm) (void)ncclCommDestroy(g.comm);
-  if(g.stream) (void)hipStreamDestroy(g.stream);
+  const std::vector<hipEvent_t> ev = std::move(g.ev);
+  const ncclComm_t comm = g.comm;
+  const hipStream_t stream = g.stream;
+  g.~Session();
+  new(&g) Session;
+  for(hipEvent_t e : ev) (void)hipEventDestroy(e);
+  if(comm) (void)ncclCommDestroy(comm);
+  if(stream) (void)hipStreamDestroy(stream);
 }
 
 // A host send must name an actor of this rank (each rank injects its own
@@ -2771,13 +2647,7 @@ int inject_locked(const gpu_msg_t* first, uint64_t n)
 {
   if(g.host_seq + n >= (1ull << 40)) return GPU_ACTOR_ERANGE;
   g.dev_epoch++;
-  if(n > g.d_msgs_cap)
-  {
-    if(g.d_msgs) HIPCK(hipFree(g.d_msgs));
-    g.d_msgs = nullptr;
-    HIPCK(hipMalloc(&g.d_msgs, n * sizeof(gpu_msg_t)));
-    g.d_msgs_cap = n;
-  }
+  if(n > g.d_msgs.size()) HIPCK(g.d_msgs.alloc(n));
   HIPCK(hipMemcpyAsync(g.d_msgs, first, n * sizeof(gpu_msg_t), hipMemcpyHostToDevice, g.stream));
   if(g.n_zones)
   {
@@ -2856,11 +2726,14 @@ GPU_ACTOR_API int gpu_actor_comm_id(void* out128)
   return 0;
 }
 
-GPU_ACTOR_API int gpu_actor_init(const gpu_actor_config_t* cfg)
+} // extern "C"
+
+namespace {
+
+// gpu_actor_init's work on a fresh session; a failure leaves what it has
+// made so far to the caller's session_end().
+int session_begin(const gpu_actor_config_t* cfg)
 {
-  std::lock_guard<std::mutex> lk(g.mu);
-  if(g.init) return GPU_ACTOR_ESTATE;
-  if(!cfg) return GPU_ACTOR_EINVAL;
   g.cfg = *cfg;
   if(g.cfg.n_ranks == 0) g.cfg.n_ranks = 1;
   if(g.cfg.rank >= g.cfg.n_ranks || g.cfg.n_ranks > kMaxRanks) return GPU_ACTOR_EINVAL;
@@ -2877,62 +2750,61 @@ GPU_ACTOR_API int gpu_actor_init(const gpu_actor_config_t* cfg)
   HIPCK(hipSetDevice(g.device));
   HIPCK(hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking));
 
-  HIPCK(hipMalloc(&g.d_stats, ST_COUNT * sizeof(unsigned long long)));
+  HIPCK(g.d_stats.alloc(ST_COUNT));
   HIPCK(hipMemsetAsync(g.d_stats, 0, ST_COUNT * sizeof(unsigned long long), g.stream));
-  HIPCK(hipMalloc(&g.d_pend, kPendSlots * sizeof(unsigned long long)));
-  HIPCK(hipMalloc(&g.d_pend_sh, (size_t)kPendSlots * kShards * sizeof(unsigned long long)));
+  HIPCK(g.d_pend.alloc(kPendSlots));
+  HIPCK(g.d_pend_sh.alloc((size_t)kPendSlots * kShards));
   HIPCK(hipMemsetAsync(g.d_pend_sh, 0, (size_t)kPendSlots * kShards * sizeof(unsigned long long),
     g.stream));
   {
     // hot-zone scratch (hot_dev.h): prep, slot, counts, key ranges (fmin
     // starts at ~0), bins, bin counts, cursors, barrier
-    const size_t words = hot_words_before_bar() + 64;
-    HIPCK(hipMalloc(&g.d_hot, words * sizeof(uint32_t)));
-    HIPCK(hipMemsetAsync(g.d_hot, 0, words * sizeof(uint32_t), g.stream));
-    uint32_t* aux = g.d_hot + 2 * kMaxZones + kMaxHot * kHotActors;
+    HIPCK(g.d_hot.alloc(kHotLayout.words));
+    HIPCK(hipMemsetAsync(g.d_hot, 0, kHotLayout.words * sizeof(uint32_t), g.stream));
+    uint32_t* aux = g.d_hot + kHotLayout.aux;
     for(uint32_t h = 0; h < kMaxHot; ++h)
       HIPCK(hipMemsetAsync(aux + (size_t)h * 3 * kHotActors, 0xFF, kHotActors * sizeof(uint32_t),
         g.stream));
   }
-  HIPCK(hipMalloc(&g.d_stats_sh, (size_t)ST_COUNT * kShards * sizeof(unsigned long long)));
+  HIPCK(g.d_stats_sh.alloc((size_t)ST_COUNT * kShards));
   HIPCK(hipMemsetAsync(g.d_stats_sh, 0, (size_t)ST_COUNT * kShards * sizeof(unsigned long long),
     g.stream));
-  HIPCK(hipMalloc(&g.d_dbg, kMaxZones * kDbgSlots * sizeof(unsigned long long)));
+  HIPCK(g.d_dbg.alloc(kMaxZones * kDbgSlots));
   HIPCK(hipMemsetAsync(g.d_dbg, 0, kMaxZones * kDbgSlots * sizeof(unsigned long long), g.stream));
-  HIPCK(hipMalloc(&g.d_spawn_n, sizeof(unsigned int)));
+  HIPCK(g.d_spawn_n.alloc(1));
   HIPCK(hipMemsetAsync(g.d_spawn_n, 0, sizeof(unsigned int), g.stream));
-  HIPCK(hipMalloc(&g.d_tstart, GPU_ACTOR_MAX_TYPES * sizeof(uint32_t)));
-  HIPCK(hipMalloc(&g.d_tcnt, GPU_ACTOR_MAX_TYPES * sizeof(uint32_t)));
-  HIPCK(hipMalloc(&g.d_live, GPU_ACTOR_MAX_TYPES * sizeof(unsigned long long)));
-  HIPCK(hipMalloc(&g.d_ctl, sizeof(SparseCtl)));
-  HIPCK(hipMalloc(&g.d_sstat, sizeof(Engine::SpillStat)));
-  HIPCK(hipMemsetAsync(g.d_sstat, 0, sizeof(Engine::SpillStat), g.stream));
-  HIPCK(hipHostMalloc(&g.h_sstat, sizeof(Engine::SpillStat), hipHostMallocDefault));
-  memset(g.h_sstat, 0, sizeof(Engine::SpillStat));
-  HIPCK(hipMalloc(&g.d_need, kMaxZones * sizeof(uint32_t)));
-  HIPCK(hipMalloc(&g.d_zplan, kMaxZones * sizeof(uint32_t)));
+  HIPCK(g.d_tstart.alloc(GPU_ACTOR_MAX_TYPES));
+  HIPCK(g.d_tcnt.alloc(GPU_ACTOR_MAX_TYPES));
+  HIPCK(g.d_live.alloc(GPU_ACTOR_MAX_TYPES));
+  HIPCK(g.d_ctl.alloc(1));
+  HIPCK(g.d_sstat.alloc(1));
+  HIPCK(hipMemsetAsync(g.d_sstat, 0, sizeof(SpillStat), g.stream));
+  HIPCK(g.h_sstat.alloc(1));
+  memset(g.h_sstat, 0, sizeof(SpillStat));
+  HIPCK(g.d_need.alloc(kMaxZones));
+  HIPCK(g.d_zplan.alloc(kMaxZones));
   HIPCK(hipMemsetAsync(g.d_zplan, 0, kMaxZones * sizeof(uint32_t), g.stream));
   g.trig_bytes = (g.cfg.max_actors + 2 * 4096 + 7) & ~7ull;   // room for either zone size
   for(int p = 0; p < 2; ++p)
   {
-    HIPCK(hipMalloc(&g.d_trig[p], g.trig_bytes));
+    HIPCK(g.d_trig[p].alloc(g.trig_bytes));
     HIPCK(hipMemsetAsync(g.d_trig[p], 0, g.trig_bytes, g.stream));
-    HIPCK(hipMalloc(&g.d_ztrig[p], kMaxZones * sizeof(uint32_t)));
+    HIPCK(g.d_ztrig[p].alloc(kMaxZones));
     HIPCK(hipMemsetAsync(g.d_ztrig[p], 0, kMaxZones * sizeof(uint32_t), g.stream));
     if(R() > 1)
     {
-      HIPCK(hipMalloc(&g.d_trig_own[p], g.trig_bytes));
+      HIPCK(g.d_trig_own[p].alloc(g.trig_bytes));
       HIPCK(hipMemsetAsync(g.d_trig_own[p], 0, g.trig_bytes, g.stream));
     }
   }
-  HIPCK(hipMalloc(&g.d_spill_flag, sizeof(unsigned int)));
+  HIPCK(g.d_spill_flag.alloc(1));
   HIPCK(hipMemsetAsync(g.d_spill_flag, 0, sizeof(unsigned int), g.stream));
-  HIPCK(hipMalloc(&g.d_trig_n, 4 * sizeof(unsigned int)));
+  HIPCK(g.d_trig_n.alloc(4));
   HIPCK(hipMemsetAsync(g.d_trig_n, 0, 4 * sizeof(unsigned int), g.stream));
-  HIPCK(hipMalloc(&g.d_bigc, kBigCopyCap * sizeof(BigCopy)));
-  HIPCK(hipMalloc(&g.d_bigc_n, 2 * sizeof(unsigned long long)));
+  HIPCK(g.d_bigc.alloc(kBigCopyCap));
+  HIPCK(g.d_bigc_n.alloc(2));
   HIPCK(hipMemsetAsync(g.d_bigc_n, 0, 2 * sizeof(unsigned long long), g.stream));
-  HIPCK(hipHostMalloc(&g.h_ctl, sizeof(SparseCtl), hipHostMallocDefault));
+  HIPCK(g.h_ctl.alloc(1));
   HIPCK(hipMemsetAsync(g.d_live, 0, GPU_ACTOR_MAX_TYPES * sizeof(unsigned long long), g.stream));
 
   if(R() > 1)
@@ -2943,14 +2815,14 @@ GPU_ACTOR_API int gpu_actor_init(const gpu_actor_config_t* cfg)
       ncclUniqueId id;
       memcpy(&id, cfg->comm_id, sizeof(id));
       NCCLCK(ncclCommInitRank(&g.comm, (int)R(), id, (int)rank()));
-      g.xp_a2a = nullptr;
-      g.xp_ar = nullptr;
+      gp.xp_a2a = nullptr;
+      gp.xp_ar = nullptr;
     }
     else
     {
       // host transport (callbacks registered with gpu_actor_set_transport);
       // its staging grows on demand (stage_room)
-      if(!g.xp_a2a || !g.xp_ar) return GPU_ACTOR_EINVAL;
+      if(!gp.xp_a2a || !gp.xp_ar) return GPU_ACTOR_EINVAL;
     }
     {
       const char* pw = getenv("PONYC_AMD_PEER_WRITE");
@@ -2958,24 +2830,23 @@ GPU_ACTOR_API int gpu_actor_init(const gpu_actor_config_t* cfg)
     }
     if(g.peer_write)
     {
-      HIPCK(hipMalloc(&g.d_pin, (size_t)R() * g.xcap * sizeof(XRec)));
-      HIPCK(hipMalloc(&g.d_hx, (1 + R()) * sizeof(unsigned long long)));
+      HIPCK(g.d_pin.alloc((size_t)R() * g.xcap));
+      HIPCK(g.d_hx.alloc(1 + R()));
     }
     else
     {
-      HIPCK(hipMalloc(&g.d_xout, (size_t)R() * g.xcap * sizeof(XRec)));
-      HIPCK(hipMalloc(&g.d_xin, (size_t)R() * g.xcap * sizeof(XRec)));
-      g.xin_cap = (uint64_t)R() * g.xcap;
+      HIPCK(g.d_xout.alloc((size_t)R() * g.xcap));
+      HIPCK(g.d_xin.alloc((size_t)R() * g.xcap));
     }
-    HIPCK(hipMalloc(&g.d_xspill_n, sizeof(unsigned int)));
+    HIPCK(g.d_xspill_n.alloc(1));
     HIPCK(hipMemsetAsync(g.d_xspill_n, 0, sizeof(unsigned int), g.stream));
     {
       const int xrc = alloc_xspill(std::max<uint32_t>(1u << 18, g.xcap / 2));
       if(xrc) return xrc;
     }
-    HIPCK(hipMalloc(&g.d_xc, (3 * R() + 3) * sizeof(unsigned long long)));
+    HIPCK(g.d_xc.alloc(3 * R() + 3));
     HIPCK(hipMemsetAsync(g.d_xc, 0, (3 * R() + 3) * sizeof(unsigned long long), g.stream));
-    HIPCK(hipHostMalloc(&g.h_xc, (3 * R() + 3) * sizeof(unsigned long long), hipHostMallocDefault));
+    HIPCK(g.h_xc.alloc(3 * R() + 3));
     g.d_xcount = g.d_xc;
     g.d_xrecv = g.d_xc + R();
     g.h_xcount.assign(R(), 0);
@@ -2994,7 +2865,23 @@ GPU_ACTOR_API int gpu_actor_init(const gpu_actor_config_t* cfg)
   return 0;
 }
 
-// Joins a finished (or running) asynchronous run; caller must NOT hold g.mu.
+} // namespace
+
+extern "C" {
+
+// All or nothing: a failure ends the session as gpu_actor_shutdown does, so
+// the engine is not initialised, holds nothing, and can be initialised again.
+GPU_ACTOR_API int gpu_actor_init(const gpu_actor_config_t* cfg)
+{
+  std::lock_guard<std::mutex> lk(gp.mu);
+  if(g.init) return GPU_ACTOR_ESTATE;
+  if(!cfg) return GPU_ACTOR_EINVAL;
+  const int rc = session_begin(cfg);
+  if(rc) session_end();
+  return rc;
+}
+
+// Joins a finished (or running) asynchronous run; caller must NOT hold gp.mu.
 // Called on the progress thread itself (the completion callback chaining a
 // run_async, wait or shutdown), it detaches instead: the thread ends right
 // after its callback returns.
@@ -3002,33 +2889,33 @@ void join_worker()
 {
   std::thread t;
   {
-    std::lock_guard<std::mutex> wl(g.wmu);
-    if(!g.worker.joinable()) return;
-    if(g.worker.get_id() == std::this_thread::get_id())
+    std::lock_guard<std::mutex> wl(gp.wmu);
+    if(!gp.worker.joinable()) return;
+    if(gp.worker.get_id() == std::this_thread::get_id())
     {
       // it cannot join itself: gpu_actor_shutdown joins it later, so its
       // completion callback has returned before anything it runs is freed
-      g.detached.push_back(std::move(g.worker));
+      gp.detached.push_back(std::move(gp.worker));
       return;
     }
-    t = std::move(g.worker);
+    t = std::move(gp.worker);
   }
   t.join();
 }
 
 // Joins the progress threads that chained runs from their callbacks (all
-// but the calling thread itself); caller must NOT hold g.mu.
+// but the calling thread itself); caller must NOT hold gp.mu.
 void join_detached()
 {
   std::vector<std::thread> ts;
   {
-    std::lock_guard<std::mutex> wl(g.wmu);
-    for(auto& t : g.detached)
+    std::lock_guard<std::mutex> wl(gp.wmu);
+    for(auto& t : gp.detached)
     {
       if(t.get_id() == std::this_thread::get_id()) t.detach();   // returns after this call
       else ts.push_back(std::move(t));
     }
-    g.detached.clear();
+    gp.detached.clear();
   }
   for(auto& t : ts)
     if(t.joinable()) t.join();
@@ -3038,67 +2925,28 @@ GPU_ACTOR_API int gpu_actor_shutdown(void)
 {
   join_worker();                      // an async run finishes first
   join_detached();
-  std::lock_guard<std::mutex> lk(g.mu);
+  std::lock_guard<std::mutex> lk(gp.mu);
   if(!g.init) return GPU_ACTOR_ESTATE;
-  if(g.stream) (void)hipStreamSynchronize(g.stream);
-  free_all();
-  for(auto& t : g.types) t = HostType();
-  g.init = false; g.n_types = 0; g.n_actors = 0; g.n_local = 0;
-  g.n_zones = 0; g.zone_records = 0; g.d_zoff = nullptr; g.d_zcap = nullptr; g.par = 0;
-  g.zbits = kZoneBits;
-  for(int p = 0; p < 2; ++p)
-  {
-    g.d_land[p] = g.d_carry[p] = nullptr;
-    g.d_land_n[p] = g.d_carry_n[p] = nullptr;
-  }
-  g.d_S = nullptr; g.d_O = nullptr;
-  g.d_stats = g.d_pend = g.d_dbg = nullptr;
-  g.d_pend_sh = g.d_stats_sh = nullptr;
-  g.d_hot = nullptr;
-  g.spawn_cap = 0; g.d_spawn_n = nullptr; g.d_tstart = g.d_tcnt = nullptr; g.d_live = nullptr;
-  g.d_ctl = nullptr; g.h_ctl = nullptr; g.sparse_launches = g.sparse_steps = 0;
-  g.d_spill[0] = g.d_spill[1] = nullptr; g.spill_cap = 0; g.d_sstat = nullptr; g.h_sstat = nullptr;
-  g.d_need = nullptr; g.zcap_min.clear(); g.zcap_host.clear(); g.fixups = 0;
-  for(int p = 0; p < 2; ++p)
-  {
-    g.d_trig[p] = g.d_trig_own[p] = nullptr;
-    g.d_ztrig[p] = nullptr;
-    g.trig_stale[p] = false;
-  }
-  g.d_zplan = nullptr;
-  g.trig_bytes = 0; g.d_muted_on = nullptr; g.muted_on_cap = 0; g.d_trig_n = nullptr; g.sidx = 0;
-  g.d_bigc = nullptr; g.d_bigc_n = nullptr; g.defer_big = false;
-  g.d_sort_tmp = nullptr; g.sort_tmp_bytes = 0;
-  for(int p = 0; p < 2; ++p) g.d_skey[p] = g.d_sarg[p] = nullptr;
-  g.h_msgs = nullptr; g.h_msgs_cap = 0; g.d_msgs = nullptr; g.d_msgs_cap = 0;
-  g.host_seq = 0; g.steps_total = 0; g.sticky = 0; g.ev.clear(); g.last_drain_ms = 0;
-  g.deferred.clear();
-  g.comm = nullptr; g.d_xout = g.d_xin = nullptr;
-  g.d_pin = nullptr; g.d_hx = nullptr; g.peer_write = false; g.d_xcount = g.d_xrecv = nullptr;
-  g.d_xc = nullptr; g.h_xc = nullptr; g.d_spill_flag = nullptr;
-  g.xcap = 0; g.remote_total = 0; g.stream = nullptr;
-  g.xin_cap = 0; g.d_xspill = nullptr; g.d_xspill_n = nullptr; g.xspill_cap = 0;
-  g.h_sbuf = g.h_rbuf = nullptr;
-  g.h_sbuf_cap = g.h_rbuf_cap = 0;
+  session_end();
   return 0;
 }
 
 GPU_ACTOR_API int gpu_actor_set_transport(gpu_actor_alltoallv_fn alltoallv,
   gpu_actor_allreduce_fn allreduce, void* ctx)
 {
-  std::lock_guard<std::mutex> lk(g.mu);
+  std::lock_guard<std::mutex> lk(gp.mu);
   if(g.init) return GPU_ACTOR_ESTATE;
   if((alltoallv == nullptr) != (allreduce == nullptr)) return GPU_ACTOR_EINVAL;
-  g.xp_a2a = alltoallv;
-  g.xp_ar = allreduce;
-  g.xp_ctx = ctx;
+  gp.xp_a2a = alltoallv;
+  gp.xp_ar = allreduce;
+  gp.xp_ctx = ctx;
   return 0;
 }
 
 GPU_ACTOR_API int gpu_actor_type_register(uint32_t type_id, uint32_t state_words,
   uint32_t handler_table)
 {
-  std::lock_guard<std::mutex> lk(g.mu);
+  std::lock_guard<std::mutex> lk(gp.mu);
   if(!g.init) return GPU_ACTOR_ESTATE;
   if(type_id >= GPU_ACTOR_MAX_TYPES) return GPU_ACTOR_EINVAL;
   const uint32_t need = required_words(handler_table);
@@ -3115,7 +2963,7 @@ GPU_ACTOR_API int gpu_actor_type_register(uint32_t type_id, uint32_t state_words
 
 GPU_ACTOR_API int gpu_actor_type_config(uint32_t type_id, uint32_t batch, uint32_t mailbox_cap)
 {
-  std::lock_guard<std::mutex> lk(g.mu);
+  std::lock_guard<std::mutex> lk(gp.mu);
   if(!g.init) return GPU_ACTOR_ESTATE;
   if(type_id >= GPU_ACTOR_MAX_TYPES || !g.types[type_id].registered) return GPU_ACTOR_EINVAL;
   HostType& t = g.types[type_id];
@@ -3128,17 +2976,17 @@ GPU_ACTOR_API int gpu_actor_type_config(uint32_t type_id, uint32_t batch, uint32
 
 GPU_ACTOR_API int gpu_actor_type_priority(uint32_t type_id, int32_t priority)
 {
-  std::lock_guard<std::mutex> lk(g.mu);
+  std::lock_guard<std::mutex> lk(gp.mu);
   if(!g.init) return GPU_ACTOR_ESTATE;
   if(type_id >= GPU_ACTOR_MAX_TYPES || !g.types[type_id].registered) return GPU_ACTOR_EINVAL;
-  if(g.async_busy) return GPU_ACTOR_EBUSY;
+  if(gp.async_busy) return GPU_ACTOR_EBUSY;
   g.types[type_id].priority = priority;
   return g.types[type_id].created ? upload_types() : 0;
 }
 
 GPU_ACTOR_API int gpu_actor_type_param(uint32_t type_id, uint32_t idx, uint64_t value)
 {
-  std::lock_guard<std::mutex> lk(g.mu);
+  std::lock_guard<std::mutex> lk(gp.mu);
   if(!g.init) return GPU_ACTOR_ESTATE;
   if(type_id >= GPU_ACTOR_MAX_TYPES || idx >= GPU_ACTOR_MAX_PARAMS ||
     !g.types[type_id].registered) return GPU_ACTOR_EINVAL;
@@ -3148,30 +2996,25 @@ GPU_ACTOR_API int gpu_actor_type_param(uint32_t type_id, uint32_t idx, uint64_t 
 
 GPU_ACTOR_API int gpu_actor_type_program(uint32_t type_id, const uint64_t* code, uint32_t n)
 {
-  std::lock_guard<std::mutex> lk(g.mu);
+  std::lock_guard<std::mutex> lk(gp.mu);
   if(!g.init) return GPU_ACTOR_ESTATE;
   if(type_id >= GPU_ACTOR_MAX_TYPES || !g.types[type_id].registered ||
      g.types[type_id].ht != GPU_ACTOR_HT_PROGRAM || !code || n <= GPU_ACTOR_PROG_ENTRIES ||
      n > (1u << 20)) return GPU_ACTOR_EINVAL;
-  if(g.async_busy) return GPU_ACTOR_EBUSY;
+  if(gp.async_busy) return GPU_ACTOR_EBUSY;
   HostType& t = g.types[type_id];
-  uint64_t* d = nullptr;
-  HIPCK(hipMalloc(&d, (size_t)n * sizeof(uint64_t)));
+  DevBuf<uint64_t> d;
+  HIPCK(d.alloc(n));
   // on the engine's stream like every other upload; the new buffer is freed
   // if the copy fails
   if(hipMemcpyAsync(d, code, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, g.stream) !=
        hipSuccess || hipStreamSynchronize(g.stream) != hipSuccess)
   {
     (void)hipGetLastError();
-    (void)hipFree(d);
     return GPU_ACTOR_EHIP;
   }
-  if(t.d_prog)
-  {
-    HIPCK(hipStreamSynchronize(g.stream));          // no launch still reads the old one
-    HIPCK(hipFree(t.d_prog));
-  }
-  t.d_prog = d;
+  if(t.d_prog) HIPCK(hipStreamSynchronize(g.stream));   // no launch still reads the old one
+  t.d_prog = std::move(d);
   t.prog_n = n;
   t.prog_host.assign(code, code + n);
   t.prog_yields = false;
@@ -3182,7 +3025,7 @@ GPU_ACTOR_API int gpu_actor_type_program(uint32_t type_id, const uint64_t* code,
 
 GPU_ACTOR_API int gpu_actor_create(uint32_t type_id, uint64_t count, uint64_t* first_id)
 {
-  std::lock_guard<std::mutex> lk(g.mu);
+  std::lock_guard<std::mutex> lk(gp.mu);
   if(!g.init) return GPU_ACTOR_ESTATE;
   if(type_id >= GPU_ACTOR_MAX_TYPES) return GPU_ACTOR_EINVAL;
   HostType& t = g.types[type_id];
@@ -3212,7 +3055,7 @@ GPU_ACTOR_API int gpu_actor_create(uint32_t type_id, uint64_t count, uint64_t* f
   t.lfirst = (uint32_t)lo;
   t.lcount = (uint32_t)(hi - lo);
   const size_t lc = std::max<size_t>(t.lcount, 1);
-  HIPCK(hipMalloc(&t.d_state, (size_t)t.words * lc * sizeof(uint64_t)));
+  HIPCK(t.d_state.alloc((size_t)t.words * lc));
   HIPCK(hipMemsetAsync(t.d_state, 0, (size_t)t.words * lc * sizeof(uint64_t), g.stream));
   t.created = true;
   g.n_actors += count;
@@ -3242,10 +3085,8 @@ GPU_ACTOR_API int gpu_actor_create(uint32_t type_id, uint64_t count, uint64_t* f
     const uint32_t cap = g.spawn_cap + (uint32_t)t.reserve;
     for(int p = 0; p < 2; ++p)
     {
-      if(g.d_skey[p]) HIPCK(hipFree(g.d_skey[p]));
-      if(g.d_sarg[p]) HIPCK(hipFree(g.d_sarg[p]));
-      HIPCK(hipMalloc(&g.d_skey[p], (size_t)cap * R() * sizeof(uint64_t)));
-      HIPCK(hipMalloc(&g.d_sarg[p], (size_t)cap * R() * sizeof(uint64_t)));
+      HIPCK(g.d_skey[p].alloc((size_t)cap * R()));
+      HIPCK(g.d_sarg[p].alloc((size_t)cap * R()));
     }
     g.spawn_cap = cap;
     rc = upload_types();
@@ -3258,7 +3099,7 @@ GPU_ACTOR_API int gpu_actor_create(uint32_t type_id, uint64_t count, uint64_t* f
 
 GPU_ACTOR_API int gpu_actor_type_reserve(uint32_t type_id, uint64_t n)
 {
-  std::lock_guard<std::mutex> lk(g.mu);
+  std::lock_guard<std::mutex> lk(gp.mu);
   if(!g.init) return GPU_ACTOR_ESTATE;
   if(type_id >= GPU_ACTOR_MAX_TYPES || !g.types[type_id].registered ||
     g.types[type_id].created) return GPU_ACTOR_EINVAL;
@@ -3269,7 +3110,7 @@ GPU_ACTOR_API int gpu_actor_type_reserve(uint32_t type_id, uint64_t n)
 
 GPU_ACTOR_API int gpu_actor_type_live(uint32_t type_id, uint64_t* live)
 {
-  std::lock_guard<std::mutex> lk(g.mu);
+  std::lock_guard<std::mutex> lk(gp.mu);
   if(!g.init) return GPU_ACTOR_ESTATE;
   if(type_id >= GPU_ACTOR_MAX_TYPES || !live || !g.types[type_id].created)
     return GPU_ACTOR_EINVAL;
@@ -3282,30 +3123,24 @@ GPU_ACTOR_API int gpu_actor_type_live(uint32_t type_id, uint64_t* live)
 
 GPU_ACTOR_API int gpu_actor_alloc_msgs(uint64_t n, gpu_msg_t** buf)
 {
-  std::lock_guard<std::mutex> lk(g.mu);
+  std::lock_guard<std::mutex> lk(gp.mu);
   if(!g.init) return GPU_ACTOR_ESTATE;
   if(!buf) return GPU_ACTOR_EINVAL;
-  if(n > g.h_msgs_cap)
-  {
-    if(g.h_msgs) HIPCK(hipHostFree(g.h_msgs));
-    g.h_msgs = nullptr;
-    HIPCK(hipHostMalloc(&g.h_msgs, n * sizeof(gpu_msg_t), hipHostMallocDefault));
-    g.h_msgs_cap = n;
-  }
+  if(n > g.h_msgs.size()) HIPCK(g.h_msgs.alloc(n));
   *buf = g.h_msgs;
   return 0;
 }
 
 GPU_ACTOR_API int gpu_actor_sendv(const gpu_msg_t* first, uint64_t n)
 {
-  std::lock_guard<std::mutex> lk(g.mu);
+  std::lock_guard<std::mutex> lk(gp.mu);
   if(!g.init) return GPU_ACTOR_ESTATE;
   return sendv_locked(first, n);
 }
 
 GPU_ACTOR_API int gpu_actor_send(uint64_t to, uint32_t behaviour, uint64_t arg)
 {
-  std::lock_guard<std::mutex> lk(g.mu);
+  std::lock_guard<std::mutex> lk(gp.mu);
   if(!g.init) return GPU_ACTOR_ESTATE;
   gpu_msg_t m;
   m.to = (uint32_t)to; m.behaviour = behaviour; m.arg = arg;
@@ -3351,7 +3186,7 @@ int run_sparse(uint64_t max_steps, SparseCtl& out)
     if(rc) return rc;
   }
   HIPCK(hipMemcpyAsync(g.h_ctl, g.d_ctl, sizeof(SparseCtl), hipMemcpyDeviceToHost, g.stream));
-  HIPCK(hipMemcpyAsync(g.h_sstat, g.d_sstat, sizeof(Engine::SpillStat), hipMemcpyDeviceToHost,
+  HIPCK(hipMemcpyAsync(g.h_sstat, g.d_sstat, sizeof(SpillStat), hipMemcpyDeviceToHost,
     g.stream));
   HIPCK(hipStreamSynchronize(g.stream));
   out = *g.h_ctl;
@@ -3393,7 +3228,7 @@ int settle_spills()
   }
   hipLaunchKernelGGL(k_spill_local, dim3(1), dim3(1), 0, g.stream, g.d_pend + kPendPre);
   HIPCK(hipGetLastError());
-  HIPCK(hipMemcpyAsync(g.h_sstat, g.d_sstat, sizeof(Engine::SpillStat), hipMemcpyDeviceToHost,
+  HIPCK(hipMemcpyAsync(g.h_sstat, g.d_sstat, sizeof(SpillStat), hipMemcpyDeviceToHost,
     g.stream));
   std::vector<unsigned long long> pv;
   const int rc = pend_read(kPendPre, 1, pv);
@@ -3401,7 +3236,7 @@ int settle_spills()
   return pv[0] ? fixup_spill() : 0;
 }
 
-// The scheduler loop to quiescence (or max_steps); caller holds g.mu.
+// The scheduler loop to quiescence (or max_steps); caller holds gp.mu.
 // One rank: chunks of kChunk k_step launches with one readback each, or
 // k_sparse launches while few records are pending. A zone that overflowed
 // halts the steps after it on the device; the host then grows the zones
@@ -3475,7 +3310,7 @@ int run_locked(uint64_t max_steps, uint64_t* steps_done)
       // every rank takes the same branch below (one rank: its own status)
       hipLaunchKernelGGL(k_spill_local, dim3(1), dim3(1), 0, g.stream, g.d_pend + k + 1);
       HIPCK(hipGetLastError());
-      HIPCK(hipMemcpyAsync(g.h_sstat, g.d_sstat, sizeof(Engine::SpillStat), hipMemcpyDeviceToHost,
+      HIPCK(hipMemcpyAsync(g.h_sstat, g.d_sstat, sizeof(SpillStat), hipMemcpyDeviceToHost,
         g.stream));
       rc = pend_read(0, k + 2, pv);
       if(rc) return rc;
@@ -3508,42 +3343,42 @@ int run_locked(uint64_t max_steps, uint64_t* steps_done)
 
 GPU_ACTOR_API int gpu_actor_run(uint64_t max_steps, uint64_t* steps_done)
 {
-  if(g.async_busy) return GPU_ACTOR_EBUSY;     // without waiting for the lock it holds
-  std::lock_guard<std::mutex> lk(g.mu);
-  if(g.async_busy) return GPU_ACTOR_EBUSY;
+  if(gp.async_busy) return GPU_ACTOR_EBUSY;     // without waiting for the lock it holds
+  std::lock_guard<std::mutex> lk(gp.mu);
+  if(gp.async_busy) return GPU_ACTOR_EBUSY;
   return run_locked(max_steps, steps_done);
 }
 
 GPU_ACTOR_API int gpu_actor_run_async(uint64_t max_steps, gpu_actor_done_fn done, void* ctx)
 {
-  if(g.async_busy) return GPU_ACTOR_EBUSY;
+  if(gp.async_busy) return GPU_ACTOR_EBUSY;
   {
-    std::lock_guard<std::mutex> lk(g.mu);
+    std::lock_guard<std::mutex> lk(gp.mu);
     if(!g.init) return GPU_ACTOR_ESTATE;
-    if(g.async_busy) return GPU_ACTOR_EBUSY;
+    if(gp.async_busy) return GPU_ACTOR_EBUSY;
   }
   join_worker();                      // reap the previous, finished run
   {
-  std::lock_guard<std::mutex> lk(g.mu);
-  if(g.async_busy) return GPU_ACTOR_EBUSY;
-  g.async_busy = true;
-  g.async_started = false;
-  g.async_rc = 0;
-  g.async_steps = 0;
+  std::lock_guard<std::mutex> lk(gp.mu);
+  if(gp.async_busy) return GPU_ACTOR_EBUSY;
+  gp.async_busy = true;
+  gp.async_started = false;
+  gp.async_rc = 0;
+  gp.async_steps = 0;
   const int dev = g.device;
   try
   {
-    std::lock_guard<std::mutex> wl(g.wmu);
-    g.worker = std::thread([max_steps, done, ctx, dev]() {
+    std::lock_guard<std::mutex> wl(gp.wmu);
+    gp.worker = std::thread([max_steps, done, ctx, dev]() {
       int rc;
       uint64_t steps = 0;
       {
-        std::lock_guard<std::mutex> wl(g.mu);
-        g.async_started = true;
+        std::lock_guard<std::mutex> wl(gp.mu);
+        gp.async_started = true;
         rc = hipSetDevice(dev) == hipSuccess ? run_locked(max_steps, &steps) : GPU_ACTOR_EHIP;
-        g.async_rc = rc;
-        g.async_steps = steps;
-        g.async_busy = false;
+        gp.async_rc = rc;
+        gp.async_steps = steps;
+        gp.async_busy = false;
       }
       // outside the lock: the callback may call back into the library
       if(done) done(ctx, rc, steps);
@@ -3551,34 +3386,34 @@ GPU_ACTOR_API int gpu_actor_run_async(uint64_t max_steps, gpu_actor_done_fn done
   }
   catch(...)
   {
-    g.async_busy = false;
+    gp.async_busy = false;
     return GPU_ACTOR_ENOMEM;
   }
   }
   // return only once the progress thread holds the lock, so every later call
   // on this library is serialised behind the run it started
-  while(!g.async_started) std::this_thread::yield();
+  while(!gp.async_started) std::this_thread::yield();
   return 0;
 }
 
 GPU_ACTOR_API int gpu_actor_wait(uint64_t* steps_done)
 {
   join_worker();
-  std::lock_guard<std::mutex> lk(g.mu);
-  if(steps_done) *steps_done = g.async_steps;
-  const int rc = g.async_rc;
-  g.async_rc = 0;
+  std::lock_guard<std::mutex> lk(gp.mu);
+  if(steps_done) *steps_done = gp.async_steps;
+  const int rc = gp.async_rc;
+  gp.async_rc = 0;
   return rc;
 }
 
 GPU_ACTOR_API int gpu_actor_busy(void)
 {
-  return g.async_busy ? 1 : 0;
+  return gp.async_busy ? 1 : 0;
 }
 
 GPU_ACTOR_API int gpu_actor_run_fixed(uint64_t n)
 {
-  std::lock_guard<std::mutex> lk(g.mu);
+  std::lock_guard<std::mutex> lk(gp.mu);
   if(!g.init) return GPU_ACTOR_ESTATE;
   {
     const int frc = flush_sends();
@@ -3652,7 +3487,7 @@ GPU_ACTOR_API int gpu_actor_run_fixed(uint64_t n)
       // the same decision on every rank (see settle_spills)
       hipLaunchKernelGGL(k_spill_local, dim3(1), dim3(1), 0, g.stream, g.d_pend + kPendPre);
       HIPCK(hipGetLastError());
-      HIPCK(hipMemcpyAsync(g.h_sstat, g.d_sstat, sizeof(Engine::SpillStat), hipMemcpyDeviceToHost,
+      HIPCK(hipMemcpyAsync(g.h_sstat, g.d_sstat, sizeof(SpillStat), hipMemcpyDeviceToHost,
         g.stream));
       std::vector<unsigned long long> pv;
       rc = pend_read(kPendPre, 1, pv);       // synchronises the stream
@@ -3683,7 +3518,7 @@ GPU_ACTOR_API int gpu_actor_run_fixed(uint64_t n)
 
 GPU_ACTOR_API int gpu_actor_sync(void)
 {
-  std::lock_guard<std::mutex> lk(g.mu);
+  std::lock_guard<std::mutex> lk(gp.mu);
   if(!g.init) return GPU_ACTOR_ESTATE;
   {
     const int frc = observe();
@@ -3696,7 +3531,7 @@ GPU_ACTOR_API int gpu_actor_sync(void)
 GPU_ACTOR_API int gpu_actor_state_read(uint32_t type_id, uint64_t first, uint64_t n,
   uint64_t* out)
 {
-  std::lock_guard<std::mutex> lk(g.mu);
+  std::lock_guard<std::mutex> lk(gp.mu);
   if(!g.init) return GPU_ACTOR_ESTATE;
   {
     const int frc = observe();
@@ -3722,7 +3557,7 @@ GPU_ACTOR_API int gpu_actor_state_read(uint32_t type_id, uint64_t first, uint64_
 GPU_ACTOR_API int gpu_actor_state_write(uint32_t type_id, uint64_t first, uint64_t n,
   const uint64_t* in)
 {
-  std::lock_guard<std::mutex> lk(g.mu);
+  std::lock_guard<std::mutex> lk(gp.mu);
   if(!g.init) return GPU_ACTOR_ESTATE;
   {
     const int frc = flush_sends();
@@ -3744,7 +3579,7 @@ GPU_ACTOR_API int gpu_actor_state_write(uint32_t type_id, uint64_t first, uint64
 
 GPU_ACTOR_API int gpu_actor_counts(gpu_actor_counts_t* out)
 {
-  std::lock_guard<std::mutex> lk(g.mu);
+  std::lock_guard<std::mutex> lk(gp.mu);
   if(!g.init) return GPU_ACTOR_ESTATE;
   {
     const int frc = observe();
@@ -3803,10 +3638,10 @@ GPU_ACTOR_API double gpu_actor_last_drain_ms(void) { return g.last_drain_ms; }
 // ---- messages to the host (include/gpu_actor_host.h) -------------------------
 GPU_ACTOR_API int gpu_actor_host_reserve(uint64_t n)
 {
-  if(g.async_busy) return GPU_ACTOR_EBUSY;
-  std::lock_guard<std::mutex> lk(g.mu);
+  if(gp.async_busy) return GPU_ACTOR_EBUSY;
+  std::lock_guard<std::mutex> lk(gp.mu);
   if(!g.init) return GPU_ACTOR_ESTATE;
-  if(g.async_busy) return GPU_ACTOR_EBUSY;
+  if(gp.async_busy) return GPU_ACTOR_EBUSY;
   // (the segments' room, reserve rounded up to kHostShards, is sorted with an int count)
   if(n == 0 || n > (1ull << 30)) return GPU_ACTOR_EINVAL;
   if(n == g.host_reserve && (!g.host_ports || g.host_seg)) return 0;
@@ -3834,7 +3669,7 @@ GPU_ACTOR_API int gpu_actor_host_reserve(uint64_t n)
 
 GPU_ACTOR_API int gpu_actor_recv(gpu_host_msg_t* out, uint64_t cap, uint64_t* n)
 {
-  std::lock_guard<std::mutex> lk(g.mu);
+  std::lock_guard<std::mutex> lk(gp.mu);
   if(!g.init) return GPU_ACTOR_ESTATE;
   if(!n || (cap && !out)) return GPU_ACTOR_EINVAL;
   *n = 0;
@@ -3854,7 +3689,7 @@ GPU_ACTOR_API int gpu_actor_recv(gpu_host_msg_t* out, uint64_t cap, uint64_t* n)
 
 GPU_ACTOR_API int gpu_actor_recv_pending(uint64_t* n)
 {
-  std::lock_guard<std::mutex> lk(g.mu);
+  std::lock_guard<std::mutex> lk(gp.mu);
   if(!g.init) return GPU_ACTOR_ESTATE;
   if(!n) return GPU_ACTOR_EINVAL;
   *n = 0;
@@ -3866,7 +3701,7 @@ GPU_ACTOR_API int gpu_actor_recv_pending(uint64_t* n)
 
 GPU_ACTOR_API int gpu_actor_host_notify(gpu_actor_host_fn fn, void* ctx)
 {
-  std::lock_guard<std::mutex> lk(g.mu);
+  std::lock_guard<std::mutex> lk(gp.mu);
   if(!g.init) return GPU_ACTOR_ESTATE;
   g.host_fn = fn;
   g.host_ctx = fn ? ctx : nullptr;
@@ -3878,7 +3713,7 @@ GPU_ACTOR_API int gpu_actor_host_notify(gpu_actor_host_fn fn, void* ctx)
 // [3] zone buffer records, [4] spill list capacity, [5] zones.
 GPU_ACTOR_API int gpu_actor_debug_info(uint64_t* out, uint64_t n)
 {
-  std::lock_guard<std::mutex> lk(g.mu);
+  std::lock_guard<std::mutex> lk(gp.mu);
   if(!g.init || !out) return GPU_ACTOR_ESTATE;
   // + the trigger counts by step index mod 3 (zone_dev.h: read this step's,
   // add to the next's, clear the one after) and the zone geometry
@@ -3923,6 +3758,15 @@ GPU_ACTOR_API int gpu_actor_debug_info(uint64_t* out, uint64_t n)
                           g.gups_in_total, g.gups_out_total, gu[2], st[ST_PLAN_ZONES]};
   for(uint64_t i = 0; i < n && i < 21; ++i) out[i] = v[i];
   return 0;
+}
+
+// Diagnostic (not in the public header): out[0] the buffers of dev_buf.h that
+// hold memory in this process, out[1] their bytes. Callable in any state.
+GPU_ACTOR_API void gpu_actor_debug_live_buffers(uint64_t out[2])
+{
+  if(!out) return;
+  out[0] = buf_live.count.load();
+  out[1] = buf_live.bytes.load();
 }
 
 // Diagnostic (not in the public header): compile the step for a program set
@@ -3996,7 +3840,7 @@ GPU_ACTOR_API int gpu_actor_debug_jit_compile_mix(uint32_t mask, int z12, const 
 // a -DGPA_STAMPS build, [n_zones][kDbgSlots] shader-clock values.
 GPU_ACTOR_API int gpu_actor_debug_stamps(uint64_t* out, uint64_t n)
 {
-  std::lock_guard<std::mutex> lk(g.mu);
+  std::lock_guard<std::mutex> lk(gp.mu);
   if(!g.init || !out) return GPU_ACTOR_ESTATE;
   n = std::min<uint64_t>(n, (uint64_t)kMaxZones * kDbgSlots);
   HIPCK(hipMemcpyAsync(out, g.d_dbg, n * sizeof(uint64_t), hipMemcpyDeviceToHost, g.stream));
@@ -4017,17 +3861,17 @@ GPU_ACTOR_API int gpu_actor_debug_stamps(uint64_t* out, uint64_t n)
 // failing call on stderr if RCCL refuses.
 GPU_ACTOR_API int gpu_actor_debug_rccl_selftest(uint64_t* out, uint64_t n)
 {
-  std::lock_guard<std::mutex> lk(g.mu);
+  std::lock_guard<std::mutex> lk(gp.mu);
   if(!g.init || !out || n < 23) return GPU_ACTOR_EINVAL;
-  if(R() != 1 || g.comm || g.xp_ar || g.xp_a2a) return GPU_ACTOR_ESTATE;
+  if(R() != 1 || g.comm || gp.xp_ar || gp.xp_a2a) return GPU_ACTOR_ESTATE;
   ncclComm_t comm = nullptr;
   int dev = g.device;
   NCCLCK(ncclCommInitAll(&comm, 1, &dev));
   g.comm = comm;
-  unsigned long long* d = nullptr;
+  DevBuf<unsigned long long> d;
   int rc = 0;
   auto run = [&]() -> int {
-    HIPCK(hipMalloc(&d, 64 * sizeof(unsigned long long)));
+    HIPCK(d.alloc(64));
     unsigned long long h[64] = {};
     for(int i = 0; i < 4; ++i) h[i] = 0x1000000000ull * (i + 1) + i;           // u64
     uint32_t* h32 = reinterpret_cast<uint32_t*>(h + 4);
@@ -4060,7 +3904,7 @@ GPU_ACTOR_API int gpu_actor_debug_rccl_selftest(uint64_t* out, uint64_t n)
     return 0;
   };
   rc = run();
-  if(d) (void)hipFree(d);
+  d.reset();
   g.comm = nullptr;
   (void)ncclCommDestroy(comm);
   return rc;

@@ -463,6 +463,18 @@ class Engine:
         self.shutdown()
 
 
+def live_buffers() -> tuple[int, int]:
+    """(buffers, bytes) of device and pinned memory the library holds in this
+    process (diagnostic export gpu_actor_debug_live_buffers; callable in any
+    state). (0, 0) after a shutdown or a failed init."""
+    fn = load_library().gpu_actor_debug_live_buffers
+    fn.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
+    fn.restype = None
+    out = (ctypes.c_uint64 * 2)()
+    fn(out)
+    return int(out[0]), int(out[1])
+
+
 def jit_compile(progs, z12: bool = False, arch: str = "gfx950", lib_path: str | None = None) -> None:
     """Compile the step for a program set (`progs`: [(type id, words), ...])
     into the library's code-object cache without a device (csrc/jit_host.h;

@@ -5,8 +5,10 @@ read from the gfx950 code objects' metadata (no GPU needed):
 
 objdir defaults to ponyc_amd/build/libgpuactor. One line per kernel:
 object, kernel (demangled), VGPRs, AGPRs, SGPRs, scratch bytes, static LDS
-bytes. Two builds' outputs diff line by line (a kernel a change must not touch
+bytes. A name past MAX_NAME characters (library templates) is cut and ends in
+a hash of the whole name. Two builds' outputs diff line by line (a kernel a change must not touch
 has to come out identical)."""
+import hashlib
 import os
 import re
 import subprocess
@@ -18,6 +20,7 @@ LLVM = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin")
 ARCH = os.environ.get("PONYC_AMD_ARCH", "gfx950")
 KEYS = [".vgpr_count", ".agpr_count", ".sgpr_count", ".private_segment_fixed_size",
         ".group_segment_fixed_size"]
+MAX_NAME = 96     # longer kernel names are cut (they run to kilobytes each)
 
 
 def kernels(obj: str, tmp: str):
@@ -68,7 +71,10 @@ def main():
                              check=True).stdout.splitlines()
     print("# object kernel vgpr agpr sgpr scratch_bytes static_lds_bytes")
     for (f, _, v), d in sorted(zip(rows, dem), key=lambda x: (x[0][0], x[1])):
-        print(f, d.replace(" ", ""), *v)
+        d = d.replace(" ", "")
+        if len(d) > MAX_NAME:       # library templates (hipcub): the head and a hash of the whole name
+            d = d[:MAX_NAME - 14] + "..#" + hashlib.sha1(d.encode()).hexdigest()[:12]
+        print(f, d, *v)
 
 
 if __name__ == "__main__":
