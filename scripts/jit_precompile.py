@@ -27,10 +27,15 @@ def sets():
         # the host-port tests' emitters (tests/test_gpu_host_port.py)
         out.append(([(0, P.emitter_program())], z12))
     out.append(([(0, edge_program())], False))
+    # the all-program spawn world (tests/test_gpu_limits.py test_spawn_high_seq)
+    from test_gpu_limits import spawn_programs
+    out.append((spawn_programs(), False))
     # any-mix engines of the tests (bit per table id): ring + FIFO source +
     # sink (test_hot_zones_past_kmaxhot), ring + spreader + fan-in sender
-    # (test_spreader_after_other_types)
-    for mask in ((1 << 1) | (1 << 9) | (1 << 10), (1 << 1) | (1 << 11) | (1 << 4)):
+    # (test_spreader_after_other_types), FIFO sink + program
+    # (test_gpu_limits.py test_spawn_high_seq)
+    for mask in ((1 << 1) | (1 << 9) | (1 << 10), (1 << 1) | (1 << 11) | (1 << 4),
+                 (1 << 10) | (1 << 12)):
         out.append((mask, False))
     # the conformance sets (tests/prog_conformance.py): three program sets and
     # the ring + program mix, at both geometries

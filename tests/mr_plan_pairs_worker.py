@@ -3,8 +3,13 @@ torch.distributed.run like tests/mr_worker.py, every rank on the one GPU over
 the host transport): 2048 * 3 pingers, so that every zone's sends to the peer
 rank go through the plan path's exchange bucket. Rank 0 checks against the
 single-rank CPU oracle and prints one `MR_RESULT {json}` line, with the zone
-steps that took the plan path summed over the ranks."""
-import ctypes
+steps that took the plan path summed over the ranks.
+
+With an argument `extra` (tests/test_gpu_limits.py): 4,096 pingers, 7 pings
+each and one more to the first `extra` ids, run one step and then to
+quiescence; the line also has the zone steps that planned in that first step
+(each rank's one zone holds 14,336 + extra / 2 messages in it, on either side
+of the two-rank sequence limit 16,382 at extra 4,090 and 4,092)."""
 import json
 import os
 import sys
@@ -20,10 +25,18 @@ import torch.distributed as dist         # noqa: E402
 from ponyc_amd import workloads as W     # noqa: E402
 from ponyc_amd.dist import GlooTransport, GlobalView   # noqa: E402
 from ponyc_amd.engine import Engine      # noqa: E402
+from test_gpu_plan_pairs import plan_zones   # noqa: E402  (this rank's zone steps that planned)
+
+
+EXTRA = int(sys.argv[1]) if len(sys.argv) > 1 else None
 
 
 def setup(e):
-    return W.ubench(e, 2048 * 3, 5, 20)
+    if EXTRA is None:
+        return W.ubench(e, 2048 * 3, 5, 20)
+    w = W.ubench(e, 4096, 7, budget=40)
+    W._sendv(e, W._msgs(w["first"] + np.arange(EXTRA, dtype=np.uint64), W.PINGER_PING, 42))
+    return w
 
 
 def main():
@@ -31,14 +44,13 @@ def main():
     rank, world = dist.get_rank(), dist.get_world_size()
     eng = Engine(device=0, n_ranks=world, rank=rank, transport=GlooTransport())
     w = setup(eng)
-    steps = eng.run(0)
+    steps, first = 0, 0
+    if EXTRA is not None:
+        steps = eng.run(1)
+        first = plan_zones(eng)
+    steps += eng.run(0)
     c = eng.counts()
-    out = (ctypes.c_uint64 * 21)()
-    fn = eng.lib.gpu_actor_debug_info
-    fn.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
-    fn.restype = ctypes.c_int
-    assert fn(out, 21) == 0
-    plan = torch.tensor([int(out[20])], dtype=torch.int64)
+    plan = torch.tensor([plan_zones(eng), first], dtype=torch.int64)
     dist.all_reduce(plan)
     res = W.ubench_result(GlobalView(eng), w)
     eng.shutdown()
@@ -59,6 +71,7 @@ def main():
             "pending": [c["pending"], co["pending"]],
             "by_type": c["delivered_by_type"] == co["delivered_by_type"],
             "dropped": c["dropped"], "remote": c["remote"], "plan_zones": int(plan[0]),
+            "plan_zones_first": int(plan[1]),
         }), flush=True)
     dist.barrier()
     dist.destroy_process_group()

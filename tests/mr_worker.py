@@ -31,6 +31,13 @@ CASES = {
     # 600 sends per source per step: sequence numbers past 511 use the high
     # bits of the 16-B cross-rank record's 14-bit seq (engine_dev.h XRec)
     "fifo_seq": (lambda e: W.fifo(e, 4, 3, 1, 600, mailbox_cap=2048), W.fifo_result, {}),
+    # 16,382 = kXSeqMax sends in one behaviour, seq 0..0x3FFD: the source on
+    # rank 1 fills all 5 high and all 9 low bits of the record's split seq on
+    # its way to the sink on rank 0 (k_xinject puts them together again); with
+    # batch 1000 the sink carries the backlog, high keys in the carry sort
+    "fifo_seq_max": (lambda e: W.fifo(e, 2, 1, 1, 16382, mailbox_cap=2048), W.fifo_result, {}),
+    "fifo_seq_max_carry": (lambda e: W.fifo(e, 2, 1, 1, 16382, batch=1000, mailbox_cap=2048),
+                           W.fifo_result, {}),
     # actors created by behaviours: every rank numbers the gathered spawn list
     "spreader": (lambda e: W.spreader(e, 10), W.spreader_result, {}),
     # backpressure across ranks: overloaded sinks mute senders on the other rank
