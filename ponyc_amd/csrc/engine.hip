@@ -239,6 +239,14 @@ __global__ void k_host_lost(unsigned long long n)
   c_eng.stats[ST_DROPPED] += n;
 }
 
+// an empty compact lane's counters: low word 0, high word land_n (EngDev::landc_n)
+__global__ void __launch_bounds__(kBlock) k_land8_mirror(const uint32_t* land_n,
+  unsigned long long* landc_n, uint32_t n)
+{
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if(i < n) landc_n[i] = (unsigned long long)land_n[i] << 32;
+}
+
 // ---- records past a zone's capacity (SpillRec, engine_dev.h) ----------------
 // need[z] = largest position + 1 spilled into zone z (either buffer)
 __global__ void __launch_bounds__(kBlock) k_spill_need(const SpillRec* s, uint32_t n, uint32_t* need)
@@ -258,6 +266,54 @@ __global__ void __launch_bounds__(kBlock) k_spill_place(const SpillRec* s, uint3
   base[c_eng.zoff[r.z] + (r.tag & kSpillPosMask)] = r.rec;
 }
 
+// The compact landing lane (EngDev::landc) of parity p back into 16-byte
+// records, one workgroup per zone: every compact record of the zone goes
+// behind its 16-byte ones in land[p] with the table's constant argument `arg`
+// (past the zone's capacity: the spill list, like any landing record); holes
+// (a chunk that did not fit the lane) are skipped. The zone's lane is then
+// empty. Launched by the host ahead of everything that reads landing buffers
+// but the step of the lane's own table (land8_flush).
+__global__ void __launch_bounds__(kBlock) k_land_expand(uint32_t p, uint64_t arg)
+{
+  // The records keep the lane's order (holes closed up): each round of kBlock
+  // places goes behind the rounds before it, a record at the number of
+  // records before it in its round (ballot per wave, the waves' counts in LDS).
+  constexpr uint32_t kWaves = kBlock / 64;
+  __shared__ uint32_t s_wave[kWaves];
+  const uint32_t z = blockIdx.x;
+  const uint32_t nlc = min((uint32_t)c_eng.landc_n[p][z], c_eng.zcapz[z]);
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  uint32_t pos0 = c_eng.land_n[p][z];
+  const uint2* const Lc = c_eng.landc[p] + c_eng.zoff[z];
+  for(uint32_t i0 = 0; i0 < nlc; i0 += kBlock)          // uniform bounds: every thread takes every round
+  {
+    const uint32_t i = i0 + threadIdx.x;
+    const uint2 r = i < nlc ? Lc[i] : make_uint2(kLand8Hole, 0u);
+    const bool rec = r.x != kLand8Hole;
+    const unsigned long long m = __ballot(rec);
+    if(lane == 0) s_wave[wv] = (uint32_t)__popcll(m);
+    __syncthreads();
+    uint32_t before = 0, round = 0;
+    for(uint32_t w = 0; w < kWaves; ++w)
+    {
+      const uint32_t c = s_wave[w];
+      if(w < wv) before += c;
+      round += c;
+    }
+    if(rec)
+      land_store(p, z, pos0 + before + (uint32_t)__popcll(m & ((1ull << lane) - 1ull)),
+        make_uint4(r.x, r.y, (uint32_t)arg, (uint32_t)(arg >> 32)));
+    pos0 += round;
+    __syncthreads();
+  }
+  if(threadIdx.x == 0)
+  {
+    c_eng.land_n[p][z] = pos0;
+    c_eng.landc_n[p][z] = (unsigned long long)pos0 << 32;
+    if(z == 0) atomicAnd(c_eng.lc_over, ~(1u << p));
+  }
+}
+
 // Backlog copies listed by k_step (EngDev::bigc, defer_big): the listed
 // records form one flat range (each copy's base, in slot order), cut into
 // equal contiguous chunks, one per workgroup; a workgroup finds the first copy
@@ -274,8 +330,7 @@ __global__ void __launch_bounds__(kBlock) k_carry_big(uint32_t cur)
 {
   // a step that did not run listed nothing (its counter may hold a list of
   // two steps before, already copied)
-  const bool halt_now = c_eng.nranks == 1 ? (c_eng.spill_n[cur] != 0u || *c_eng.halt != 0u)
-                                          : (*c_eng.spill_flag != 0u);
+  const bool halt_now = c_eng.nranks == 1 ? step_halted(cur) : (*c_eng.spill_flag != 0u);
   if(halt_now) return;
   const unsigned long long v = c_eng.bigc_n[cur];  // final: k_step ran to completion before
   const uint32_t n = min((uint32_t)(v >> 32), c_eng.bigc_cap);
@@ -340,7 +395,7 @@ struct HostType {
 struct SpillStat {
   unsigned int spill_n[2];
   unsigned int halt;
-  unsigned int pad;
+  unsigned int lc_over;        // bit p: the compact lane of parity p needs the host (EngDev::lc_over)
   unsigned long long skipped;
 };
 
@@ -403,6 +458,14 @@ struct Session {
   DevBuf<uint32_t> d_zcap;
   DevBuf<ZRec> d_land[2], d_carry[2];
   DevBuf<uint32_t> d_land_n[2], d_carry_n[2];
+  // the compact landing lane (EngDev::landc): allocated with
+  // the zone buffers for a table whose sends carry a constant argument;
+  // land8: the step uses it (one rank; PONYC_AMD_LAND8=0 turns it off);
+  // land8_dirty: a step ran since the lane was last expanded (land8_flush)
+  DevBuf<uint2> d_landc[2];
+  DevBuf<unsigned long long> d_landc_n[2];
+  bool land8 = false, land8_dirty = false;
+  uint64_t land8_arg = 0;               // the lane's table's constant argument (StepEntry::plan_arg)
   DevBuf<ZRec> d_S;
   DevBuf<ORec> d_O;
   uint32_t par = 0;                     // parity the next step reads
@@ -759,6 +822,8 @@ int gups_apply_launch(hipEvent_t e1)
   return 0;
 }
 
+bool land8_table();
+
 int upload_types()
 {
   TypeDev td[GPU_ACTOR_MAX_TYPES];
@@ -826,6 +891,13 @@ int upload_types()
   e.spill_cap = g.spill_cap;
   e.xspill = g.d_xspill; e.xspill_n = g.d_xspill_n; e.xspill_cap = g.xspill_cap;
   e.zbits = g.zbits;
+  {
+    g.land8 = land8_table() && g.d_landc[0] && g.d_landc[1] && g.d_sstat;
+    if(g.land8) g.land8_arg = pick_step_entry().plan_arg;
+    e.land8 = g.land8 ? 1u : 0u;
+    for(int p = 0; p < 2; ++p) { e.landc[p] = g.d_landc[p]; e.landc_n[p] = g.d_landc_n[p]; }
+    e.lc_over = g.d_sstat ? &g.d_sstat->lc_over : nullptr;
+  }
   g.defer_big = defer_big_wanted();
   // k_hot runs where backlogs build (the same engines as defer_big);
   // PONYC_AMD_HOT=0/1 forces it (tests, A/B)
@@ -902,6 +974,8 @@ int ensure_spill(uint64_t cap)
 }
 
 int relayout_zones(bool geometry = false);
+int land8_flush();
+bool land8_table();
 StepEntry step_entry_for(bool z12);
 bool step_fits(const StepEntry& se, uint64_t nb);
 int upload_types();
@@ -924,7 +998,30 @@ int read_sstat()
 
 inline bool spill_pending()
 {
-  return g.h_sstat->spill_n[0] || g.h_sstat->spill_n[1] || g.h_sstat->halt;
+  return g.h_sstat->spill_n[0] || g.h_sstat->spill_n[1] || g.h_sstat->halt || g.h_sstat->lc_over;
+}
+
+// Whether the engine's step is that of a table with a compact landing lane.
+// (With n_ranks > 1 only a rank's own zones have one: a peer's records stay
+// 16-byte XRecs, which k_xinject lands in land[]; a lane that needs the host
+// on any rank halts every rank's next step, k_spill_flag.)
+bool land8_table()
+{
+  const char* f = getenv("PONYC_AMD_LAND8");
+  return pick_step_entry().const_arg && !(f && atoi(f) == 0);
+}
+
+// Empty the compact lane of both parities into the 16-byte landing buffers
+// (k_land_expand), when a step may have written it since the last time.
+int land8_flush()
+{
+  if(!g.land8 || !g.land8_dirty || g.n_zones == 0) return 0;
+  for(uint32_t p = 0; p < 2; ++p)
+    hipLaunchKernelGGL(k_land_expand, dim3(g.n_zones), dim3(kBlock), 0, g.stream, p, g.land8_arg);
+  HIPCK(hipGetLastError());
+  g.land8_dirty = false;
+  g.dev_epoch++;
+  return 0;
 }
 
 // Grow every zone that spilled, land the spilled records at the positions
@@ -936,6 +1033,16 @@ inline bool spill_pending()
 // with nothing of its own to land, so that every rank's next step runs alike.
 int fixup_spill()
 {
+  // the compact lane first: what does not fit its zone joins the spill lists
+  // (this rank's own word: a rank whose lanes fit has nothing to expand)
+  if(g.h_sstat->lc_over)
+  {
+    g.land8_dirty = true;
+    int rc = land8_flush();
+    if(rc) return rc;
+    rc = read_sstat();
+    if(rc) return rc;
+  }
   const SpillStat st = *g.h_sstat;
   g.dev_epoch++;
   if(R() == 1 && !st.spill_n[0] && !st.spill_n[1] && !st.halt) return 0;
@@ -1029,6 +1136,7 @@ uint32_t pick_zone_bits(uint64_t n)
 bool zones_empty()
 {
   if(g.n_zones == 0) return true;
+  if(land8_flush() != 0) return false;
   std::vector<uint32_t> v(g.n_zones);
   for(int p = 0; p < 2; ++p)
     for(const uint32_t* src : {g.d_land_n[p].get(), g.d_carry_n[p].get()})
@@ -1054,6 +1162,11 @@ int relayout_zones(bool geometry)
   // whether mail has landed anywhere is summed over ranks (create is called
   // by every rank alike, so this collective is reached by all of them).
   bool fresh = false;
+  // (the compact lane's records move as 16-byte ones: expanded in the old layout)
+  {
+    const int rc = land8_flush();
+    if(rc) return rc;
+  }
   {
     const uint32_t want = pick_zone_bits((g.n_actors + R() - 1) / R());
     if(geometry && want != g.zbits && g.steps_total == 0 && g.sparse_launches == 0)
@@ -1138,6 +1251,19 @@ int relayout_zones(bool geometry)
     }
     HIPCK(hipStreamSynchronize(g.stream));
   }
+  DevBuf<uint2> lc[2];
+  DevBuf<unsigned long long> lcn[2];
+  if(land8_table())
+    for(int p = 0; p < 2; ++p)
+    {
+      HIPCK(lc[p].alloc(recs));
+      HIPCK(lcn[p].alloc(nzn));
+      // empty lane; the high words mirror land_n
+      hipLaunchKernelGGL(k_land8_mirror, dim3(blocks_for(nzn)), dim3(kBlock), 0, g.stream,
+        (const uint32_t*)ln[p], (unsigned long long*)lcn[p], (uint32_t)nzn);
+      HIPCK(hipGetLastError());
+      HIPCK(hipStreamSynchronize(g.stream));
+    }
   HIPCK(S.alloc(3 * recs));                // 2 x: records of a zone; 1 x: sort scratch
   HIPCK(O.alloc(recs));
   // the receiver each muted actor waits on, one word per local slot
@@ -1158,6 +1284,7 @@ int relayout_zones(bool geometry)
   {
     g.d_land[p].swap(land[p]); g.d_carry[p].swap(carry[p]);
     g.d_land_n[p].swap(ln[p]); g.d_carry_n[p].swap(cn[p]);
+    g.d_landc[p].swap(lc[p]); g.d_landc_n[p].swap(lcn[p]);
   }
   g.d_S.swap(S);
   g.d_O.swap(O);
@@ -1265,9 +1392,10 @@ int check_sticky()
 //   lets every rank's next k_step halt alike when any zone overflowed.
 // The host transport (gpu_actor_set_transport) does the same through its
 // callbacks, with the records staged through pinned host memory.
+// (a compact lane that needs the host counts like a spill list in use: EngDev::lc_over)
 __global__ void k_spill_flag(unsigned int* flag)
 {
-  *flag = c_eng.spill_n[0] + c_eng.spill_n[1];
+  *flag = c_eng.spill_n[0] + c_eng.spill_n[1] + (c_eng.land8 ? *c_eng.lc_over : 0u);
 }
 
 // This rank's spill status as one number (zone spill lists, halt, and the
@@ -1536,7 +1664,7 @@ __global__ void __launch_bounds__(256) k_gups_apply_ranks(const uint64_t* list, 
 __global__ void k_spill_local(unsigned long long* out)
 {
   *out = (unsigned long long)c_eng.spill_n[0] + c_eng.spill_n[1] + *c_eng.halt +
-         (c_eng.nranks > 1 ? *c_eng.spill_flag : 0u);
+         (c_eng.land8 ? *c_eng.lc_over : 0u) + (c_eng.nranks > 1 ? *c_eng.spill_flag : 0u);
 }
 
 // Only when the exchange spill list itself overflowed (records were lost and
@@ -2356,6 +2484,7 @@ int launch_step(uint32_t slot, hipEvent_t e0, hipEvent_t e1)
   g.dev_epoch++;
   const StepEntry se = pick_step_entry();
   if(se.stub) return GPU_ACTOR_EINVAL;      // an experiment build without this table
+  if(g.land8) g.land8_dirty = true;
   // bucket arrays (4 x buckets — an order-free zone's two passes need no
   // more: zone_dev.h two_pass; six for a message-local table's, dp_table)
   // and, for hot receivers, the sort's work area
@@ -3165,6 +3294,10 @@ bool sparse_ok()
 int run_sparse(uint64_t max_steps, SparseCtl& out)
 {
   g.dev_epoch++;
+  {
+    const int rc = land8_flush();          // k_sparse reads 16-byte landing records only
+    if(rc) return rc;
+  }
   bool prog = false, gups = false;
   for(const HostType& t : g.types)
   {
@@ -3752,11 +3885,13 @@ GPU_ACTOR_API int gpu_actor_debug_info(uint64_t* out, uint64_t n)
   }
   HIPCK(hipMemcpyAsync(st, g.d_stats, sizeof(st), hipMemcpyDeviceToHost, g.stream));
   HIPCK(hipStreamSynchronize(g.stream));
-  const uint64_t v[21] = {g.fixups, g.sparse_launches, g.sparse_steps, g.zone_records, g.spill_cap,
+  // + [21] landing records taken from the compact lane (EngDev::landc)
+  const uint64_t v[22] = {g.fixups, g.sparse_launches, g.sparse_steps, g.zone_records, g.spill_cap,
                           g.n_zones, tn[0], tn[1], tn[2], g.zbits, hb[3], g.hot_on ? 1u : 0u,
                           g.jit_used ? 1u : 0u, g.jit_builds, gu[0], gu[1], g.peer_write ? 1u : 0u,
-                          g.gups_in_total, g.gups_out_total, gu[2], st[ST_PLAN_ZONES]};
-  for(uint64_t i = 0; i < n && i < 21; ++i) out[i] = v[i];
+                          g.gups_in_total, g.gups_out_total, gu[2], st[ST_PLAN_ZONES],
+                          st[ST_LAND8]};
+  for(uint64_t i = 0; i < n && i < 22; ++i) out[i] = v[i];
   return 0;
 }
 

@@ -59,6 +59,7 @@ enum Stat : int {
   ST_SEQ_OVERFLOW = 5, ST_XCHG_OVERFLOW = 6, ST_ACTIVE = 7,
   ST_ATOMICS = 8,        // global reservation atomics issued by k_step
   ST_PLAN_ZONES = 9,     // zone steps that took the two-pass plan path (gpu_actor_debug_info)
+  ST_LAND8 = 10,         // landing records a zone took from the compact lane (EngDev::landc)
   ST_BY_TYPE = 16, ST_COUNT = 32
 };
 
@@ -290,7 +291,34 @@ struct EngDev {
   uint4* host_rec;
   unsigned int* host_n;           // [kHostShards] records listed (may count past host_seg)
   const uint64_t* host_step;
+  // The compact landing lane (land8 set: one table whose sends
+  // all carry plan_const_arg; a peer rank's records stay XRecs and land as
+  // 16-byte ones). landc[p] holds 8-byte records
+  // {w0, from} — a ZRec without its argument — in land's zone geometry;
+  // landc_n[p][z]: low word the compact records reserved in zone z, high word
+  // a mirror of land_n[p][z] (every 16-byte reservation adds to both:
+  // land_reserve), so whoever reserves last sees the zone's whole mail. A
+  // reservation that finds the two lanes together past the zone's capacity,
+  // or a compact chunk past it, sets bit p of *lc_over: the next step then
+  // halts like one that finds a spill list in use (n_ranks > 1: on every
+  // rank, the word is summed into spill_flag), and the host expands the lane
+  // into land[p] (k_land_expand) and grows the zone.
+  uint2* landc[2];
+  unsigned long long* landc_n[2];
+  unsigned int* lc_over;
+  uint32_t land8, pad10;
 };
+constexpr uint32_t kLand8Hole = 0xFFFFFFFFu;   // w0 of a compact place no record was stored at
+// Whether this code object can run in a land8 session: the step of the table
+// with the lane and the host's helper kernels; every other step (and the
+// run-time compiled ones) compiles as it did without the lane.
+#if defined(__HIPCC_RTC__)
+constexpr bool kLand8Code = false;
+#elif defined(GPA_STEP_HT)
+constexpr bool kLand8Code = (GPA_STEP_HT) == GPU_ACTOR_HT_PINGER;
+#else
+constexpr bool kLand8Code = true;
+#endif
 constexpr uint32_t kHostShards = 64;
 constexpr uint32_t kGupsShards = 64;
 constexpr uint32_t kShards = 32;
@@ -540,6 +568,27 @@ __device__ __forceinline__ uint32_t xout_store(uint32_t peer, uint32_t pos, cons
   return 0;
 }
 
+// Reserve h 16-byte landing records of zone b, parity p: their first position.
+__device__ __forceinline__ uint32_t land_reserve(uint32_t p, uint32_t b, uint32_t h)
+{
+  const uint32_t base = atomicAdd(&c_eng.land_n[p][b], h);
+  if(kLand8Code && c_eng.land8)
+  {
+    const unsigned long long o = atomicAdd(&c_eng.landc_n[p][b], (unsigned long long)h << 32);
+    const uint64_t all = (o & 0xFFFFFFFFull) + (o >> 32) + h;
+    if((uint32_t)o != 0u && all > c_eng.zcapz[b]) atomicOr(c_eng.lc_over, 1u << p);
+  }
+  return base;
+}
+
+// A step does not run while a spill list of its parity is in use, the compact
+// lane of its parity needs the host, or an earlier step was skipped (one rank).
+__device__ __forceinline__ bool step_halted(uint32_t cur)
+{
+  if(c_eng.spill_n[cur] != 0u || *c_eng.halt != 0u) return true;
+  return kLand8Code && c_eng.land8 && ((*c_eng.lc_over >> cur) & 1u) != 0u;
+}
+
 // Store landing record v of zone z at reserved position pos of parity p.
 __device__ __forceinline__ void land_store(uint32_t p, uint32_t z, uint32_t pos, const uint4& v)
 {
@@ -559,7 +608,7 @@ __device__ __forceinline__ void send_direct(uint32_t nxt, uint32_t self, uint32_
   const uint32_t b = bucket_of(to);
   if(b < nz)
   {
-    const uint32_t pos = atomicAdd(&c_eng.land_n[nxt][b], 1u);
+    const uint32_t pos = land_reserve(nxt, b, 1u);
     uint4 v;
     v.x = w | slot_in_zone(rdiv(to));
     v.y = self;

@@ -102,7 +102,7 @@ __device__ void sp_land(const SpList& l, uint32_t n, uint32_t p)
   {
     const uint32_t L = (uint32_t)(l.K[i] >> 32);
     const uint32_t z = zone_of_local(L);
-    const uint32_t pos = atomicAdd(&c_eng.land_n[p][z], 1u);
+    const uint32_t pos = land_reserve(p, z, 1u);
     uint4 v;
     v.x = l.W[i] | slot_in_zone(L);
     v.y = (uint32_t)l.K[i];
@@ -242,7 +242,8 @@ __global__ void __launch_bounds__(kSpThreads) k_sparse(uint32_t cur, unsigned lo
   // spilled records wait for the host; an actor that triggers muting
   // (overloaded or muted) needs the zone path's backpressure
   const bool pending_fixup = c_eng.spill_n[cur] != 0u || *c_eng.halt != 0u ||
-                             c_eng.trig_n[sidx % 3u] != 0u;
+                             c_eng.trig_n[sidx % 3u] != 0u ||
+                             (c_eng.land8 && *c_eng.lc_over != 0u);
   if(__syncthreads_or(carried) || total > kSpCap || pending_fixup)
   {
     // the dense path owns this step: nothing was touched
@@ -262,7 +263,11 @@ __global__ void __launch_bounds__(kSpThreads) k_sparse(uint32_t cur, unsigned lo
     bW[0][i] = v.x & ~zm;
     bA[0][i] = ((uint64_t)v.w << 32) | v.z;
   }
-  for(uint32_t z = z0; z < z1; ++z) c_eng.land_n[cur][z] = 0;
+  for(uint32_t z = z0; z < z1; ++z)
+  {
+    c_eng.land_n[cur][z] = 0;
+    if(c_eng.land8) c_eng.landc_n[cur][z] = 0ull;
+  }
   // no actor triggers muting now; bytes a zone left in the other parity two
   // steps ago are cleared, so both parities read as all-quiet when the zone
   // path resumes

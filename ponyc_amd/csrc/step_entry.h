@@ -30,6 +30,11 @@ struct StepEntry {
   // split tables: the step as two launches (zone_dev.h k_step PM 1, 2), or
   // as one that calls the second's code (PM 3); nullptr for the other tables
   step_kernel_t plan, rest, fused;
+  // a two-pass table whose sends all carry one constant argument: its engines
+  // keep a compact landing lane, and plan_arg is that argument (zone_dev.h
+  // plan_const_arg), which k_land_expand puts back
+  bool const_arg;
+  uint64_t plan_arg;
 };
 
 namespace gpa {

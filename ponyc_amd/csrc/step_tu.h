@@ -37,6 +37,10 @@ template <int HT, int PM> constexpr step_kernel_t split_kernel()
 #endif
 
 namespace {
+template <int HT> constexpr uint64_t step_plan_arg()
+{
+  if constexpr(HT >= 0 && two_pass<HT>()) return plan_const_arg<HT>(); else return 0;
+}
 hipError_t step_upload(const void* types, const void* eng, hipStream_t s)
 {
   const hipError_t e = hipMemcpyToSymbolAsync(HIP_SYMBOL(c_types), types,
@@ -48,14 +52,16 @@ hipError_t step_upload(const void* types, const void* eng, hipStream_t s)
 
 #if GPA_STEP_STUB
 StepEntry GPA_STEP_ENTRY() { return { k_step_stub<GPA_STEP_HT>, step_upload, true, (uint32_t)kZoneBits,
-                                      (uint32_t)kZoneThreads, kSortWork, 4u, false, nullptr, nullptr, nullptr }; }
+                                      (uint32_t)kZoneThreads, kSortWork, 4u, false, nullptr, nullptr, nullptr, false, 0 }; }
 #else
 StepEntry GPA_STEP_ENTRY() { return { k_step<GPA_STEP_HT, 0>, step_upload, false, (uint32_t)kZoneBits,
                                       (uint32_t)kZoneThreads, kSortWork,
                                       dp_table<GPA_STEP_HT>() ? 6u : 4u,
                                       GPA_STEP_HT < 0 || GPA_STEP_HT == kHtFifoPair,
                                       split_kernel<GPA_STEP_HT, 1>(), split_kernel<GPA_STEP_HT, 2>(),
-                                      split_kernel<GPA_STEP_HT, 3>() }; }
+                                      split_kernel<GPA_STEP_HT, 3>(),
+                                      GPA_STEP_HT >= 0 && two_pass<GPA_STEP_HT>(),
+                                      step_plan_arg<GPA_STEP_HT>() }; }
 #endif
 
 } // namespace gpa

@@ -260,6 +260,11 @@ __device__ __forceinline__ void st16(uint4* p, const uint4& v)
 {
   p->x = v.x; p->y = v.y; p->z = v.z; p->w = v.w;
 }
+// an 8-byte record as one vector store
+__device__ __forceinline__ void st8(uint2* p, const uint2& v)
+{
+  *reinterpret_cast<uint64_t*>(p) = ((uint64_t)v.y << 32) | v.x;
+}
 __device__ __forceinline__ uint4 ld16(const uint4* p)
 {
   uint4 v;
@@ -1210,20 +1215,36 @@ __device__ __forceinline__ uint32_t emit_rec(const uint4& r, uint32_t b, uint32_
 // the reserved position itself (a peer rank's segment, or a chunk that
 // reaches past the zone: emit_rec checks each record).
 constexpr uint32_t kDirect = 0x80000000u;
+// C8 (the plan path of a table with plan_const_arg): a direct chunk may lie in
+// the compact lane instead (EngDev::landc, the same record offset; kCompact),
+// and a direct chunk's offset then has 30 bits.
+constexpr uint32_t kCompact = 0x40000000u;
+template <bool C8 = false>
 __device__ __forceinline__ uint32_t chunk_dst(uint32_t b, uint32_t base, uint32_t h, uint32_t nz)
 {
   if(b < nz)
   {
     const uint64_t o = c_eng.zoff[b] + base;
-    if(base + h <= c_eng.zcapz[b] && o + h <= 0x7FFFFFFFull) return (uint32_t)o | kDirect;
+    if(base + h <= c_eng.zcapz[b] && o + h <= (C8 ? 0x3FFFFFFFull : 0x7FFFFFFFull))
+      return (uint32_t)o | kDirect;
   }
   return base;
 }
 
 // Record r of bucket b at offset rel past its chunk's destination word d.
+template <bool C8 = false>
 __device__ __forceinline__ uint32_t emit_at(const uint4& r, uint32_t b, uint32_t d, uint32_t rel,
   uint32_t L0, uint32_t nz, uint32_t nxt)
 {
+  if constexpr(C8)
+    if((d & (kDirect | kCompact)) == (kDirect | kCompact))
+    {
+      // the record without its argument, one 8-byte store
+      st8(c_eng.landc[nxt] + ((d & ~(kDirect | kCompact)) + rel),
+          make_uint2((r.y & ~kZoneMask) | (rdiv(r.x) & kZoneMask),
+                     (L0 + (r.y & kZoneMask)) * c_eng.nranks + c_eng.rank));
+      return 0;
+    }
   if(d & kDirect)
   {
     uint4 v;
@@ -1279,7 +1300,8 @@ struct TileCtx : ActorBase {
     if(idx < tcap)
       tile[idx] = r;
     else
-      xover += emit_at(tile_rec16(r, kArg), b, bs[b], idx - ((st[b] >> sh) & 0xFFFFu), L0, nz, nxt);
+      xover += emit_at<sizeof(Rec) == sizeof(uint2)>(tile_rec16(r, kArg), b, bs[b],
+                 idx - ((st[b] >> sh) & 0xFFFFu), L0, nz, nxt);
   }
 };
 
@@ -1289,7 +1311,12 @@ struct TileCtx : ActorBase {
 // (rh[0, nb) rounds 0-1, rh[nb, 2nb) rounds 2-3), the plan path's two
 // super-rounds in one.
 // (1) one chunk per bucket for the zone's sends: bs[b] = chunk_dst word
-template <int NW>
+// C8: a local zone's chunk goes to the compact lane when the session has one
+// (EngDev::land8) and the chunk fits the zone there; one 64-bit add reserves
+// it and returns the zone's 16-byte records beside it. A chunk that does not
+// fit marks the places it was given within the lane as holes, asks for the
+// host (lc_over) and goes the 16-byte way like any chunk before this lane.
+template <int NW, bool C8 = false>
 __device__ __forceinline__ uint32_t plan_reserve(const uint32_t* rh, uint32_t* bs, uint32_t nb,
   uint32_t nz, uint32_t nxt, uint32_t tid)
 {
@@ -1308,11 +1335,29 @@ __device__ __forceinline__ uint32_t plan_reserve(const uint32_t* rh, uint32_t* b
     {
       ++n_atom;
       if(b < nz)
-        base = atomicAdd(&c_eng.land_n[nxt][b], h);
+      {
+        if constexpr(C8)
+          if(c_eng.land8)
+          {
+            const unsigned long long o = atomicAdd(&c_eng.landc_n[nxt][b], (unsigned long long)h);
+            const uint32_t bc = (uint32_t)o, capb = c_eng.zcapz[b];
+            const uint64_t off = c_eng.zoff[b] + bc;
+            if((uint64_t)bc + h <= capb && off + h <= 0x3FFFFFFFull)
+            {
+              if((uint64_t)bc + h + (o >> 32) > capb) atomicOr(c_eng.lc_over, 1u << nxt);
+              bs[b] = (uint32_t)off | kDirect | kCompact;
+              continue;
+            }
+            atomicOr(c_eng.lc_over, 1u << nxt);
+            for(uint32_t q = bc; q < capb && q - bc < h; ++q)
+              c_eng.landc[nxt][c_eng.zoff[b] + q] = make_uint2(kLand8Hole, 0u);
+          }
+        base = land_reserve(nxt, b, h);
+      }
       else
         base = (uint32_t)atomicAdd(&c_eng.xcount[b - nz], (unsigned long long)h);
     }
-    bs[b] = chunk_dst(b, base, h, nz);
+    bs[b] = chunk_dst<C8>(b, base, h, nz);
   }
   return n_atom;
 }
@@ -1393,7 +1438,8 @@ __device__ __forceinline__ uint32_t plan_emit(const Rec* tile, uint32_t m, const
       if(q < m)
       {
         const uint32_t b = bucket_of(rec[u].x);
-        xover += emit_at(tile_rec16(rec[u], kArg), b, bsr[b], q - ((rst[b] >> sh) & 0xFFFFu), L0, nz, nxt);
+        xover += emit_at<sizeof(Rec) == sizeof(uint2)>(tile_rec16(rec[u], kArg), b, bsr[b],
+                   q - ((rst[b] >> sh) & 0xFFFFu), L0, nz, nxt);
       }
     }
   }
@@ -1528,8 +1574,7 @@ __device__ __forceinline__ bool zone_step(const uint32_t z, uint32_t cur, uint32
   // by skipped steps, so every zone of a launch decides alike).
   // With n_ranks > 1 the decision is the spill flag summed over ranks after
   // the last exchange, so every rank halts the same steps.
-  const bool halt_now = c_eng.nranks == 1 ? (c_eng.spill_n[cur] != 0u || *c_eng.halt != 0u)
-                                          : (*c_eng.spill_flag != 0u);
+  const bool halt_now = c_eng.nranks == 1 ? step_halted(cur) : (*c_eng.spill_flag != 0u);
   if(halt_now)
   {
     if(PM != 1 && z == 0 && tid == 0)
@@ -1598,7 +1643,34 @@ __device__ __forceinline__ bool zone_step(const uint32_t z, uint32_t cur, uint32
 
   // ---- 1. count --------------------------------------------------------------
   const uint32_t nc = min(rfl(c_eng.carry_n[cur][z]), cap);
-  const uint32_t nl = min(rfl(c_eng.land_n[cur][z]), cap);
+  // A session with a compact lane (EngDev::land8): the zone's landed mail is
+  // nl16 16-byte records and then nlc compact ones. The plan path counts them
+  // where they lie; a zone step that may read whole records (PM 2; PM 0 once
+  // it has left the plan path) first expands the compact ones into land[cur]
+  // at [nl16, nl16 + nlc) with the table's constant argument — nothing else
+  // writes parity cur of this zone during the step, and a step runs only when
+  // both lanes together fit the zone (lc_over, step_halted).
+  constexpr bool kL8 = HTS >= 0 && two_pass<HTS>();
+  const uint32_t nl16 = min(rfl(c_eng.land_n[cur][z]), cap);
+  uint32_t nlc = 0;
+  if constexpr(kL8)
+    if(c_eng.land8) nlc = min(rfl((uint32_t)c_eng.landc_n[cur][z]), cap - nl16);
+  const uint32_t nl = nl16 + nlc;
+  auto expand8 = [&]() __attribute__((always_inline)) {
+    if constexpr(kL8)
+    {
+      const uint2* const Lc = c_eng.landc[cur] + zo;
+      uint4* const Lx = reinterpret_cast<uint4*>(c_eng.land[cur] + zo + nl16);
+      constexpr uint64_t kA = plan_const_arg<kL8 ? HTS : GPU_ACTOR_HT_PINGER>();
+      for(uint32_t i = tid; i < nlc; i += kZoneThreads)
+      {
+        const uint2 r = Lc[i];
+        st16(Lx + i, make_uint4(r.x, r.y, (uint32_t)kA, (uint32_t)(kA >> 32)));
+      }
+      __syncthreads();
+    }
+  };
+  if constexpr(PM == 2) { if(nlc) expand8(); }
   if(nc + nl == 0 && ztc == 0)
   {
     if constexpr(PM == 1) return false;
@@ -1624,6 +1696,7 @@ __device__ __forceinline__ bool zone_step(const uint32_t z, uint32_t cur, uint32
       reinterpret_cast<uint32_t*>(s_tb)[i] = 0;
   const ZRec* C = c_eng.carry[cur] + zo;
   const ZRec* Ld = c_eng.land[cur] + zo;
+  const uint2* const Lc8 = kL8 && c_eng.land8 ? c_eng.landc[cur] + zo : nullptr;
   const bool use_idx = kSimple || nc + nl <= kIdxCap;       // uniform per workgroup
   // a hot zone k_hot prepared: its arrivals are in S already, counted in
   // hot_cnt, each big group sorted (hot_dev.h)
@@ -1756,7 +1829,10 @@ __device__ __forceinline__ bool zone_step(const uint32_t z, uint32_t cur, uint32
     for(int u = 0; u < kIdxPer; ++u)
     {
       const uint32_t i = u * kZoneThreads + tid;
-      wr[u] = i < nl ? Ld[i].w0 : 0xFFFFFFFFu;
+      if constexpr(kL8 && PM != 2)
+        wr[u] = i < nl16 ? Ld[i].w0 : i < nl ? Lc8[i - nl16].x : 0xFFFFFFFFu;
+      else
+        wr[u] = i < nl ? Ld[i].w0 : 0xFFFFFFFFu;
     }
 #pragma unroll
     for(int u = 0; u < kIdxPer; ++u)
@@ -1780,7 +1856,10 @@ __device__ __forceinline__ bool zone_step(const uint32_t z, uint32_t cur, uint32
     for(int u = 0; u < kUnroll; ++u)
     {
       const uint32_t i = base + u * kZoneThreads + tid;
-      w[u] = i < nl ? Ld[i].w0 : 0xFFFFFFFFu;
+      if constexpr(kL8 && PM != 2)
+        w[u] = i < nl16 ? Ld[i].w0 : i < nl ? Lc8[i - nl16].x : 0xFFFFFFFFu;
+      else
+        w[u] = i < nl ? Ld[i].w0 : 0xFFFFFFFFu;
     }
     // (a hot receiver's arrivals: lanes of one actor folded into one atomic)
 #pragma unroll
@@ -1844,6 +1923,9 @@ __device__ __forceinline__ bool zone_step(const uint32_t z, uint32_t cur, uint32
       if constexpr(two_pass<HTS>())
         plan = PM != 2 && fast && s_tot < c_eng.seq_max && c_eng.two_pass != 0u;
     }
+  // (one kernel for every path: a zone that leaves the plan path here reads
+  // whole records from now on)
+  if constexpr(PM == 0 && kL8) { if(!plan && nlc) expand8(); }
   if constexpr(PM == 1)
   {
     if constexpr(kPlanSplit)
@@ -2160,7 +2242,7 @@ __device__ __forceinline__ bool zone_step(const uint32_t z, uint32_t cur, uint32
       lds_sync();
       GPA_STAMP(3);
       // one chunk per bucket for the zone's sends
-      n_atom += plan_reserve<1>(s_rh, s_bs, nb, nz, nxt, tid);
+      n_atom += plan_reserve<1, true>(s_rh, s_bs, nb, nz, nxt, tid);
       GPA_STAMP(5);
 #ifdef GPA_STAMPS
       const unsigned long long t_scan = __builtin_amdgcn_s_memtime();
@@ -2720,7 +2802,7 @@ __device__ __forceinline__ bool zone_step(const uint32_t z, uint32_t cur, uint32
     if(h)
     {
       ++n_atom;
-      const uint32_t base = b < nz ? atomicAdd(&c_eng.land_n[nxt][b], h)
+      const uint32_t base = b < nz ? land_reserve(nxt, b, h)
                                    : (uint32_t)atomicAdd(&c_eng.xcount[b - nz], (unsigned long long)h);
       s_base[b] = chunk_dst(b, base, h, nz);
     }
@@ -2825,8 +2907,10 @@ __device__ __forceinline__ bool zone_step(const uint32_t z, uint32_t cur, uint32
     if(nc + nl) pend_add_z(pend_slot, z, (unsigned long long)(nc + nl));
     c_eng.carry_n[cur][z] = 0;
     c_eng.land_n[cur][z] = 0;
+    if constexpr(kL8) { if(c_eng.land8) c_eng.landc_n[cur][z] = 0ull; }
     if constexpr(PM == 1) c_eng.zplan[z] = sidx + 1u;
   }
+  if constexpr(kL8) { if(took_mail && nlc && tid == 7) stat_add_z(ST_LAND8, z, (unsigned long long)nlc); }
 #ifdef GPA_STAMPS
   if(tid == 0) c_eng.dbg[z * kDbgSlots + 12] = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -2872,7 +2956,9 @@ __global__ void __launch_bounds__(kBlock) k_pending(uint32_t cur, uint32_t slot)
   if(z < c_eng.n_zones)
   {
     const uint32_t cap = zone_capacity(z);
-    p = min(c_eng.carry_n[cur][z], cap) + min(c_eng.land_n[cur][z], cap);
+    const uint32_t nl16 = min(c_eng.land_n[cur][z], cap);
+    p = min(c_eng.carry_n[cur][z], cap) + nl16;
+    if(c_eng.land8) p += min((uint32_t)c_eng.landc_n[cur][z], cap - nl16);
   }
   p = wave_sum(p);
   if(__lane_id() == 0) s_red[threadIdx.x >> 6] = p;
@@ -2918,7 +3004,7 @@ __device__ __forceinline__ void land_records(LandRec (&r)[kLandPer], uint32_t cu
     }
   __syncthreads();
   for(uint32_t b = threadIdx.x; b < nz; b += kLandThreads)
-    if(s_hist[b]) s_base[b] = atomicAdd(&c_eng.land_n[cur][b], s_hist[b]);
+    if(s_hist[b]) s_base[b] = land_reserve(cur, b, s_hist[b]);
   __syncthreads();
 #pragma unroll
   for(int u = 0; u < kLandPer; ++u)

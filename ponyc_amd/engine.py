@@ -431,11 +431,16 @@ class Engine:
         self._host_thunk = thunk      # the library holds the pointer until it is replaced
 
     def debug_info(self) -> dict:
-        """Engine internals (diagnostic export, not in include/gpu_actor.h)."""
+        """Engine internals (diagnostic export, not in include/gpu_actor.h).
+
+        land8_records: compact landing records that zone steps took from the
+        lane (counted by the reader; records the host expanded back into
+        16-byte ones with k_land_expand are not in it)."""
         keys = ["fixups", "sparse_launches", "sparse_steps", "zone_records", "spill_cap", "zones",
                 "trig_n0", "trig_n1", "trig_n2", "zone_bits", "hot_missed", "hot_on", "jit",
                 "jit_builds", "gups_updates", "gups_atomics", "peer_write",
-                "gups_chunks_in", "gups_chunks_out", "gups_remote"]
+                "gups_chunks_in", "gups_chunks_out", "gups_remote", "plan_zones",
+                "land8_records"]
         out = (ctypes.c_uint64 * len(keys))()
         fn = self.lib.gpu_actor_debug_info
         fn.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
