@@ -164,7 +164,8 @@ GPU_ACTOR_API int gpu_actor_create(uint32_t type_id, uint64_t count, uint64_t* f
  * sequence) order after the type's live actors; its constructor message is
  * delivered in the next superstep like any other send. With n_ranks > 1
  * every rank gathers every rank's spawn records and numbers them alike, so
- * the ids equal a single rank's; the owner (id % n_ranks) lands the message. */
+ * the ids equal a single rank's; the owner (gpu_actor_owner(id)) lands the
+ * message, at its next local slot of the type. */
 GPU_ACTOR_API int gpu_actor_type_reserve(uint32_t type_id, uint64_t n);
 /* Live (created + spawned) actors of a type. */
 GPU_ACTOR_API int gpu_actor_type_live(uint32_t type_id, uint64_t* live);
@@ -220,7 +221,9 @@ GPU_ACTOR_API int gpu_actor_state_read(uint32_t type_id, uint64_t first, uint64_
 GPU_ACTOR_API int gpu_actor_state_write(uint32_t type_id, uint64_t first, uint64_t n,
   const uint64_t* in);
 GPU_ACTOR_API int gpu_actor_counts(gpu_actor_counts_t* out);
-/* Id of the rank owning actor `id` (hash partition; id % n_ranks). */
+/* Id of the rank owning actor `id` under the session's placement: block
+ * (id >> b) % n_ranks, b chosen with gpu_actor_place_blocks
+ * (gpu_actor_place.h); id % n_ranks by default. */
 GPU_ACTOR_API uint32_t gpu_actor_owner(uint64_t id);
 /* Device stream the engine runs on (hipStream_t), for profiling/overlap. */
 GPU_ACTOR_API void* gpu_actor_stream(void);

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/gpu_actor_host.h"
+#include "../../include/gpu_actor_place.h"
 #include "engine_dev.h"
 #include "zone_dev.h"
 #include "sparse_dev.h"
@@ -62,7 +63,7 @@ __global__ void __launch_bounds__(kBlock) k_construct_table(uint32_t t, uint32_t
   {
     const uint64_t k = x / n, li = x - k * n;
     const uint64_t L = T.lfirst + li;
-    const uint64_t i = L * c_eng.nranks + c_eng.rank - T.first;
+    const uint64_t i = global_of((uint32_t)L) - T.first;
     if(i >= live) continue;
     T.state[x] = k + i * size;
   }
@@ -77,7 +78,7 @@ __global__ void __launch_bounds__(kBlock) k_construct(uint32_t t, uint32_t live)
   const uint32_t li = blockIdx.x * kBlock + threadIdx.x;
   if(li >= T.lcount) return;
   const uint32_t L = T.lfirst + li;
-  const uint64_t i = (uint64_t)L * c_eng.nranks + c_eng.rank - T.first;   // index in type
+  const uint64_t i = global_of(L) - T.first;   // index in type
   if(i >= live) return;
   const size_t n = T.lcount;
   uint64_t* st = T.state;
@@ -166,7 +167,7 @@ __global__ void __launch_bounds__(kLandThreads) k_spawn_land(const uint64_t* key
       if(slot < T.count)
       {
         // every rank numbers the same gathered list; it lands its own actors
-        r[u].valid = c_eng.nranks == 1 || (T.first + slot) % c_eng.nranks == c_eng.rank;
+        r[u].valid = !is_remote(T.first + (uint32_t)slot);
         r[u].to = T.first + (uint32_t)slot;
         r[u].w = (uint32_t)(((k >> 4) & 0xFFFFull) << 16) | (uint32_t)((k & 0xFu) << 12);
         r[u].from = (uint32_t)(k >> 20);
@@ -436,6 +437,9 @@ struct Process {
   gpu_actor_alltoallv_fn xp_a2a = nullptr;
   gpu_actor_allreduce_fn xp_ar = nullptr;
   void* xp_ctx = nullptr;
+  // placement of the sessions to come (gpu_actor_place_blocks; -1: never
+  // called, PONYC_AMD_BLOCK_BITS or 0)
+  int place_bits = -1;
 };
 
 // One engine, from gpu_actor_init to gpu_actor_shutdown (or to a failed init):
@@ -451,6 +455,9 @@ struct Session {
   uint32_t n_types = 0;                 // 1 + highest created type id
   uint64_t n_actors = 0;                // global ids handed out
   uint32_t n_local = 0;
+  // placement of this session (gpu_actor_place_blocks, verified equal on
+  // every rank by init)
+  uint32_t block_bits = 0;
   // zones
   uint32_t n_zones = 0;
   uint64_t zone_records = 0;
@@ -651,10 +658,44 @@ Session& g = *new Session;
 inline uint32_t R() { return g.cfg.n_ranks; }
 inline uint32_t rank() { return g.cfg.rank; }
 
+// The placement (include/gpu_actor_place.h): blocks of 2^b consecutive ids
+// dealt round-robin over n ranks. Pure functions of (n, b): the public
+// gpu_actor_place_map / _global and the session's own bookkeeping.
+inline uint32_t place_owner(uint32_t n, uint32_t b, uint64_t id) { return (uint32_t)((id >> b) % n); }
+inline uint64_t place_slot(uint32_t n, uint32_t b, uint64_t id)
+{
+  return (((id >> b) / n) << b) | (id & ((1ull << b) - 1));
+}
+inline uint64_t place_global(uint32_t n, uint32_t b, uint32_t r, uint64_t slot)
+{
+  return ((((slot >> b) * n) + r) << b) | (slot & ((1ull << b) - 1));
+}
+// number of ids < x owned by rank r: its whole blocks below x's block, and
+// the part of x's block below x if that block is r's
+inline uint64_t place_below(uint32_t n, uint32_t b, uint32_t r, uint64_t x)
+{
+  const uint64_t f = x >> b;
+  return ((f > r ? (f - r + n - 1) / n : 0) << b) + (f % n == r ? x & ((1ull << b) - 1) : 0);
+}
+
 // number of ids < x owned by this rank
 inline uint64_t owned_below(uint64_t x)
 {
-  return x > rank() ? (x - rank() + R() - 1) / R() : 0;
+  return place_below(R(), g.block_bits, rank(), x);
+}
+
+// n_ranks > 1: some rank owns none of the ids handed out (fewer blocks of
+// ids than ranks, under any placement). Such a rank has no zone and launches
+// no step, and a step's exchange needs every rank: the run calls refuse such
+// a world (run_locked, gpu_actor_run_fixed). Every rank computes the same
+// answer from the same global values, so all refuse alike, before any
+// collective. (A world without any actor has nothing to run on any rank.)
+inline bool rank_without_actors()
+{
+  if(R() == 1 || g.n_actors == 0) return false;
+  for(uint32_t r = 0; r < R(); ++r)
+    if(place_below(R(), g.block_bits, r, g.n_actors) == 0) return true;
+  return false;
 }
 
 inline uint32_t blocks_for(uint64_t n, uint32_t bs = kBlock) { return (uint32_t)((n + bs - 1) / bs); }
@@ -891,6 +932,7 @@ int upload_types()
   e.spill_cap = g.spill_cap;
   e.xspill = g.d_xspill; e.xspill_n = g.d_xspill_n; e.xspill_cap = g.xspill_cap;
   e.zbits = g.zbits;
+  e.block_bits = g.block_bits;
   {
     g.land8 = land8_table() && g.d_landc[0] && g.d_landc[1] && g.d_sstat;
     if(g.land8) g.land8_arg = pick_step_entry().plan_arg;
@@ -1157,8 +1199,9 @@ int relayout_zones(bool geometry)
   // the geometry may change only before any step ran, with no mail landed
   // (zone buffers are copied zone by zone below)
   // Every rank must pick the same geometry (the trigger-byte merge and the
-  // bucket layout assume it), so the choice follows the largest rank's share,
-  // ceil(n_actors / R), not this rank's own count, which can be one less; and
+  // bucket layout assume it), so the choice follows the largest rank's share
+  // (rank 0's: ceil(n_actors / R) with single-id blocks), not this rank's own
+  // count, which can be less; and
   // whether mail has landed anywhere is summed over ranks (create is called
   // by every rank alike, so this collective is reached by all of them).
   bool fresh = false;
@@ -1168,7 +1211,7 @@ int relayout_zones(bool geometry)
     if(rc) return rc;
   }
   {
-    const uint32_t want = pick_zone_bits((g.n_actors + R() - 1) / R());
+    const uint32_t want = pick_zone_bits(place_below(R(), g.block_bits, 0, g.n_actors));
     if(geometry && want != g.zbits && g.steps_total == 0 && g.sparse_launches == 0)
     {
       HIPCK(hipStreamSynchronize(g.stream));
@@ -1619,7 +1662,7 @@ __global__ void __launch_bounds__(256) k_gups_apply_ranks(const uint64_t* list, 
           }
           if(to - u_first < u_count)
             w = reinterpret_cast<unsigned long long*>(
-              &u_state[(v & u_mask) * u_lcount + (rdiv(to) - u_lfirst)]);
+              &u_state[(v & u_mask) * u_lcount + (slot_of(to) - u_lfirst)]);
         }
       }
       const uint64_t wa = reinterpret_cast<uint64_t>(w);
@@ -1899,13 +1942,12 @@ int xc_sendrecv(const std::vector<XcPeer>& pp)
   return 0;
 }
 
-// Trigger bytes in use: global ids L * R + r for every local slot L of the
-// largest rank's zones (the same count on every rank, as the merge needs).
+// Trigger bytes in use: a rank writes the bytes of its own actors' global ids
+// (global_of of its local slots below n_local), all below n_actors under any
+// placement (the same count on every rank, as the merge needs).
 uint64_t trig_live_bytes()
 {
-  const uint64_t per_rank = (g.n_actors + R() - 1) / R();
-  const uint64_t zones = (per_rank + zone_actors() - 1) / zone_actors();
-  return std::min<uint64_t>(g.trig_bytes, (zones * zone_actors() * R() + 7) & ~7ull);
+  return std::min<uint64_t>(g.trig_bytes, (g.n_actors + 7) & ~7ull);
 }
 
 // Peer writes: map every peer's inbox (hipIpcGetMemHandle / hipIpcOpenMemHandle),
@@ -2769,7 +2811,7 @@ inline bool host_msg_ok(const gpu_msg_t& m)
   if(m.to - g.eng_host.host_first < g.eng_host.host_span)
     for(uint32_t k = 0; k < g.eng_host.host_nrng; ++k)
       if(m.to - g.eng_host.host_rng[k].first < g.eng_host.host_rng[k].count) return false;
-  return m.to < g.n_actors && m.behaviour <= 0xF && (R() == 1 || m.to % R() == rank());
+  return m.to < g.n_actors && m.behaviour <= 0xF && (R() == 1 || place_owner(R(), g.block_bits, m.to) == rank());
 }
 
 int inject_locked(const gpu_msg_t* first, uint64_t n)
@@ -2870,6 +2912,14 @@ int session_begin(const gpu_actor_config_t* cfg)
   if(g.cfg.mailbox_cap == 0) g.cfg.mailbox_cap = 16;
   if(g.cfg.max_actors == 0) g.cfg.max_actors = 1ull << 26;
   if(g.cfg.max_actors > 0xFF000000ull) return GPU_ACTOR_EINVAL;
+  if(gp.place_bits >= 0)
+    g.block_bits = (uint32_t)gp.place_bits;
+  else if(const char* f = getenv("PONYC_AMD_BLOCK_BITS"))   // test hook: the default placement
+  {
+    const int b = atoi(f);
+    if(b < 0 || b > (int)GPU_ACTOR_PLACE_MAX_BITS) return GPU_ACTOR_EINVAL;
+    g.block_bits = (uint32_t)b;
+  }
 
   int ndev = 0;
   if(hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return GPU_ACTOR_ENODEV;
@@ -2980,6 +3030,21 @@ int session_begin(const gpu_actor_config_t* cfg)
     g.d_xrecv = g.d_xc + R();
     g.h_xcount.assign(R(), 0);
     g.h_xrecv.assign(R(), 0);
+    {
+      // one placement on every rank: with b and b^2 summed over ranks, all
+      // b are equal iff (sum b)^2 == R * sum b^2 (Cauchy-Schwarz); every rank
+      // sees the same sums, so all fail or none
+      unsigned long long v[2] = {g.block_bits, (unsigned long long)g.block_bits * g.block_bits};
+      unsigned long long* dc = g.d_xc + 2 * R();         // scratch words of the counts block
+      HIPCK(hipMemcpyAsync(dc, v, sizeof(v), hipMemcpyHostToDevice, g.stream));
+      const int prc = xc_allreduce_sum(dc, dc, 2, XC_U64);
+      if(prc) return prc;
+      HIPCK(hipMemcpyAsync(v, dc, sizeof(v), hipMemcpyDeviceToHost, g.stream));
+      HIPCK(hipStreamSynchronize(g.stream));
+      const bool same = v[0] * v[0] == (unsigned long long)R() * v[1];
+      HIPCK(hipMemsetAsync(dc, 0, sizeof(v), g.stream));
+      if(!same) return GPU_ACTOR_EINVAL;
+    }
     if(g.peer_write)
     {
       HIPCK(hipStreamSynchronize(g.stream));
@@ -3377,6 +3442,7 @@ int settle_spills()
 int run_locked(uint64_t max_steps, uint64_t* steps_done)
 {
   if(!g.init) return GPU_ACTOR_ESTATE;
+  if(rank_without_actors()) return GPU_ACTOR_EINVAL;
   {
     const int frc = observe();
     if(frc) return frc;
@@ -3548,6 +3614,7 @@ GPU_ACTOR_API int gpu_actor_run_fixed(uint64_t n)
 {
   std::lock_guard<std::mutex> lk(gp.mu);
   if(!g.init) return GPU_ACTOR_ESTATE;
+  if(n && rank_without_actors()) return GPU_ACTOR_EINVAL;
   {
     const int frc = flush_sends();
     if(frc) return frc;
@@ -3761,7 +3828,44 @@ GPU_ACTOR_API int gpu_actor_counts(gpu_actor_counts_t* out)
 GPU_ACTOR_API uint32_t gpu_actor_owner(uint64_t id)
 {
   const uint32_t r = g.cfg.n_ranks ? g.cfg.n_ranks : 1;
-  return (uint32_t)(id % r);
+  return place_owner(r, g.block_bits, id);
+}
+
+// ---- placement (include/gpu_actor_place.h) -----------------------------------
+GPU_ACTOR_API int gpu_actor_place_blocks(uint32_t block_bits)
+{
+  std::lock_guard<std::mutex> lk(gp.mu);
+  if(block_bits > GPU_ACTOR_PLACE_MAX_BITS) return GPU_ACTOR_EINVAL;
+  if(g.init) return GPU_ACTOR_ESTATE;
+  gp.place_bits = (int)block_bits;
+  return 0;
+}
+
+GPU_ACTOR_API int gpu_actor_place_map(uint32_t n_ranks, uint32_t block_bits, uint64_t id,
+  uint32_t* rank, uint64_t* slot)
+{
+  if(n_ranks == 0 || block_bits > GPU_ACTOR_PLACE_MAX_BITS) return GPU_ACTOR_EINVAL;
+  if(rank) *rank = place_owner(n_ranks, block_bits, id);
+  if(slot) *slot = place_slot(n_ranks, block_bits, id);
+  return 0;
+}
+
+GPU_ACTOR_API int gpu_actor_place_global(uint32_t n_ranks, uint32_t block_bits, uint32_t rank,
+  uint64_t slot, uint64_t* id)
+{
+  if(n_ranks == 0 || rank >= n_ranks || block_bits > GPU_ACTOR_PLACE_MAX_BITS || !id)
+    return GPU_ACTOR_EINVAL;
+  *id = place_global(n_ranks, block_bits, rank, slot);
+  return 0;
+}
+
+GPU_ACTOR_API int gpu_actor_place_below(uint32_t n_ranks, uint32_t block_bits, uint32_t rank,
+  uint64_t id, uint64_t* n)
+{
+  if(n_ranks == 0 || rank >= n_ranks || block_bits > GPU_ACTOR_PLACE_MAX_BITS || !n)
+    return GPU_ACTOR_EINVAL;
+  *n = place_below(n_ranks, block_bits, rank, id);
+  return 0;
 }
 
 GPU_ACTOR_API void* gpu_actor_stream(void) { return (void*)g.stream; }
@@ -3886,12 +3990,13 @@ GPU_ACTOR_API int gpu_actor_debug_info(uint64_t* out, uint64_t n)
   HIPCK(hipMemcpyAsync(st, g.d_stats, sizeof(st), hipMemcpyDeviceToHost, g.stream));
   HIPCK(hipStreamSynchronize(g.stream));
   // + [21] landing records taken from the compact lane (EngDev::landc)
-  const uint64_t v[22] = {g.fixups, g.sparse_launches, g.sparse_steps, g.zone_records, g.spill_cap,
+  // + [22] the session's placement (gpu_actor_place_blocks)
+  const uint64_t v[23] = {g.fixups, g.sparse_launches, g.sparse_steps, g.zone_records, g.spill_cap,
                           g.n_zones, tn[0], tn[1], tn[2], g.zbits, hb[3], g.hot_on ? 1u : 0u,
                           g.jit_used ? 1u : 0u, g.jit_builds, gu[0], gu[1], g.peer_write ? 1u : 0u,
                           g.gups_in_total, g.gups_out_total, gu[2], st[ST_PLAN_ZONES],
-                          st[ST_LAND8]};
-  for(uint64_t i = 0; i < n && i < 22; ++i) out[i] = v[i];
+                          st[ST_LAND8], g.block_bits};
+  for(uint64_t i = 0; i < n && i < 23; ++i) out[i] = v[i];
   return 0;
 }
 

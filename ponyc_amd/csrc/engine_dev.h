@@ -1,7 +1,9 @@
 // engine_dev.h — device-side data layout, delivery primitives and handler
 // tables of the gpu_actor engine. See DESIGN.md for the rationale.
 //
-// HBM layout (per rank; actor id a lives on rank a % R at local slot L = a / R):
+// HBM layout (per rank; blocks of 2^b consecutive actor ids live together on a
+// rank, dealt round-robin: owner_of / slot_of / global_of below; b = 0, the
+// default, puts id a on rank a % R at local slot L = a / R):
 //   Local slots are cut into zones of kZone actors (2048, or 4096 for large
 //   engines: step_entry.h). Zone z owns
 //     land[p][z]   : landing buffer of step-p arrivals (unordered 16-B ZRecs),
@@ -307,6 +309,9 @@ struct EngDev {
   unsigned long long* landc_n[2];
   unsigned int* lc_over;
   uint32_t land8, pad10;
+  // block-cyclic placement (include/gpu_actor_place.h): blocks of
+  // 1 << block_bits consecutive ids share a rank (0: id % nranks)
+  uint32_t block_bits, pad11;
 };
 constexpr uint32_t kLand8Hole = 0xFFFFFFFFu;   // w0 of a compact place no record was stored at
 // Whether this code object can run in a land8 session: the step of the table
@@ -331,17 +336,42 @@ constexpr uint32_t kHotMin = 32768;
 __constant__ TypeDev c_types[GPU_ACTOR_MAX_TYPES];
 __constant__ EngDev  c_eng;
 
-// x / nranks and x % nranks without a division instruction sequence: for
-// 32-bit x, mulhi(x, floor(2^64 / d) + 1) is exact (Lemire's fastdiv).
+// x / nranks without a division instruction sequence: for 32-bit x,
+// mulhi(x, floor(2^64 / d) + 1) is exact (Lemire's fastdiv).
 __device__ __forceinline__ uint32_t rdiv(uint32_t x)
 {
-  return c_eng.nranks == 1 ? x : (uint32_t)__umul64hi(c_eng.r_magic, (uint64_t)x);
+  return (uint32_t)__umul64hi(c_eng.r_magic, (uint64_t)x);
 }
 
-__device__ __forceinline__ uint32_t rmod(uint32_t x)
+// Placement (include/gpu_actor_place.h): with b = block_bits, q = id >> b and
+// o = id & (2^b - 1), id lives on rank q % R at local slot (q / R) << b | o;
+// global_of is the inverse for this rank's slots. q < 2^32, so rdiv is exact.
+// With one rank all three are the identity (slot_of and owner_of behind one
+// uniform test, as the division always was).
+__device__ __forceinline__ uint32_t slot_of(uint32_t id)
 {
-  return x - rdiv(x) * c_eng.nranks;
+  const uint32_t b = c_eng.block_bits;
+  return c_eng.nranks == 1 ? id : (rdiv(id >> b) << b) | (id & ((1u << b) - 1u));
 }
+
+__device__ __forceinline__ uint32_t owner_of(uint32_t id)
+{
+  const uint32_t q = id >> c_eng.block_bits;
+  return c_eng.nranks == 1 ? 0u : q - rdiv(q) * c_eng.nranks;
+}
+
+// The id at local slot L of rank r (k_xinject: a peer's sender), of this rank:
+// (((L >> b) * R + r) << b) | (L & (2^b - 1)), written as L plus its block
+// index times the other ranks' share of a round, plus r's offset in the
+// round — two uniform factors, and the identity with one rank without a test
+// (the drains and the emit loops compute it per actor and per record).
+__device__ __forceinline__ uint32_t global_on(uint32_t r, uint32_t L)
+{
+  const uint32_t b = c_eng.block_bits;
+  return L + (L >> b) * ((c_eng.nranks - 1u) << b) + (r << b);
+}
+
+__device__ __forceinline__ uint32_t global_of(uint32_t L) { return global_on(c_eng.rank, L); }
 
 __device__ __forceinline__ int type_of_local(uint32_t L)
 {
@@ -391,10 +421,10 @@ __device__ __forceinline__ uint32_t bucket_of(uint32_t to)
   const uint32_t R = c_eng.nranks;
   if(R > 1)
   {
-    const uint32_t owner = rmod(to);
+    const uint32_t owner = owner_of(to);
     if(owner != c_eng.rank) return c_eng.n_zones + owner;
   }
-  return zone_of_local(rdiv(to));
+  return zone_of_local(slot_of(to));
 }
 
 // Cross-rank record from global ids and a (seq << 16 | beh << 12) word.
@@ -402,8 +432,8 @@ __device__ __forceinline__ XRec xpack(uint32_t to, uint32_t w, uint32_t from, ui
 {
   const uint32_t seq = (w >> 16) == kSeqApply ? kXSeqApply : (w >> 16);
   XRec x;
-  x.w0 = (seq >> 9) << 27 | ((w >> 12) & 0xFu) << 23 | rdiv(to);
-  x.w1 = (seq & 0x1FFu) << 23 | rdiv(from);
+  x.w0 = (seq >> 9) << 27 | ((w >> 12) & 0xFu) << 23 | slot_of(to);
+  x.w1 = (seq & 0x1FFu) << 23 | slot_of(from);
   x.arg = arg;
   return x;
 }
@@ -475,7 +505,7 @@ __device__ __forceinline__ void reducible_apply_local(uint32_t to, uint32_t beh,
   const int t = type_of_global(to);
   if(t < 0) return;
   const TypeDev& T = c_types[t];
-  const uint32_t li = rdiv(to) - T.lfirst;
+  const uint32_t li = slot_of(to) - T.lfirst;
   switch(T.ht)
   {
     case GPU_ACTOR_HT_FANIN_ANALYZER:
@@ -610,7 +640,7 @@ __device__ __forceinline__ void send_direct(uint32_t nxt, uint32_t self, uint32_
   {
     const uint32_t pos = land_reserve(nxt, b, 1u);
     uint4 v;
-    v.x = w | slot_in_zone(rdiv(to));
+    v.x = w | slot_in_zone(slot_of(to));
     v.y = self;
     v.z = (uint32_t)arg;
     v.w = (uint32_t)(arg >> 32);
@@ -698,7 +728,7 @@ __device__ __forceinline__ void spawn_actor(A& a, uint32_t type, uint32_t beh, u
 
 __device__ __forceinline__ bool is_remote(uint32_t to)
 {
-  return c_eng.nranks > 1 && rmod(to) != c_eng.rank;
+  return c_eng.nranks > 1 && owner_of(to) != c_eng.rank;
 }
 
 // A program's SEND to a host port (include/gpu_actor_host.h): pony_sendv
@@ -826,7 +856,7 @@ __device__ __forceinline__ void send_analyzer(A& a, uint32_t to, uint64_t arg)
       if(t >= 0)
       {
         const TypeDev& T = c_types[t];
-        const uint32_t li = rdiv(tl) - T.lfirst;
+        const uint32_t li = slot_of(tl) - T.lfirst;
         if(a.fan && t == a.fan_t && li < kFanLds)
         {
           // zone accumulator: one global atomic per (zone, analyzer) at the end
@@ -873,7 +903,7 @@ __device__ __forceinline__ void send_updater(A& a, uint32_t to, uint64_t d)
   // one serialised atomic per update). The path of a streamer whose list
   // segment is full, or with PONYC_AMD_GUPS_DEFER=0: listed chunks go through
   // k_gups_apply / k_gups_apply_ranks instead.
-  const uint32_t li = rdiv(to) - a.rc_lfirst;
+  const uint32_t li = slot_of(to) - a.rc_lfirst;
   if(d != 0)
     atomicXor(reinterpret_cast<unsigned long long*>(&a.rc_state[(d & a.rc_mask) * a.rc_lcount + li]),
       (unsigned long long)d);

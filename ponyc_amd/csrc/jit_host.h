@@ -325,6 +325,14 @@ inline int load(const std::string& src, const char* k1, const char* k2, const st
     log += "\nmodule load failed";
     return GPU_ACTOR_EHIP;
   }
+  // a module built against another layout of the constants (a stale cache
+  // entry, a header that went out of step) would read the wrong fields
+  if(m.eng_sz != sizeof(gpa::EngDev) || m.types_sz != sizeof(gpa::TypeDev) * GPU_ACTOR_MAX_TYPES)
+  {
+    (void)hipModuleUnload(m.mod);
+    log += "\nmodule's constants differ in size from the library's";
+    return GPU_ACTOR_EINVAL;
+  }
   int a = 0, b = 0;
   if(hipFuncGetAttribute(&a, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, m.plan) == hipSuccess &&
      (!m.rest || hipFuncGetAttribute(&b, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, m.rest) == hipSuccess))

@@ -84,7 +84,7 @@ struct SparseCtx : ActorBase {
     const uint32_t i = atomicAdd(&sp_cnt[__builtin_amdgcn_readfirstlane(q)], 1u);
     if(i < kSpCap)
     {
-      nx.K[i] = ((uint64_t)rdiv(to) << 32) | self; nx.W[i] = w; nx.A[i] = arg;
+      nx.K[i] = ((uint64_t)slot_of(to) << 32) | self; nx.W[i] = w; nx.A[i] = arg;
     }
     else
     {
@@ -421,7 +421,7 @@ __global__ void __launch_bounds__(kSpThreads) k_sparse(uint32_t cur, unsigned lo
       const int t = sp_type(s_tinfo, n_types, L);
       SparseCtx a;
       a.reset_common();
-      a.self = L * c_eng.nranks + c_eng.rank;
+      a.self = global_of(L);
       a.src_local = slot_in_zone(L);
       a.type = t;
       a.agg = &s_agg[wv];

@@ -1190,11 +1190,11 @@ __device__ __forceinline__ uint4 tile_rec16(const uint2& r, uint64_t arg)
 __device__ __forceinline__ uint32_t emit_rec(const uint4& r, uint32_t b, uint32_t pos, uint32_t L0,
   uint32_t nz, uint32_t nxt)
 {
-  const uint32_t from = (L0 + (r.y & kZoneMask)) * c_eng.nranks + c_eng.rank;
+  const uint32_t from = global_of(L0 + (r.y & kZoneMask));
   if(b < nz)
   {
     uint4 v;
-    v.x = (r.y & ~kZoneMask) | (rdiv(r.x) & kZoneMask);
+    v.x = (r.y & ~kZoneMask) | (slot_of(r.x) & kZoneMask);
     v.y = from;
     v.z = r.z;
     v.w = r.w;
@@ -1241,15 +1241,15 @@ __device__ __forceinline__ uint32_t emit_at(const uint4& r, uint32_t b, uint32_t
     {
       // the record without its argument, one 8-byte store
       st8(c_eng.landc[nxt] + ((d & ~(kDirect | kCompact)) + rel),
-          make_uint2((r.y & ~kZoneMask) | (rdiv(r.x) & kZoneMask),
-                     (L0 + (r.y & kZoneMask)) * c_eng.nranks + c_eng.rank));
+          make_uint2((r.y & ~kZoneMask) | (slot_of(r.x) & kZoneMask),
+                     global_of(L0 + (r.y & kZoneMask))));
       return 0;
     }
   if(d & kDirect)
   {
     uint4 v;
-    v.x = (r.y & ~kZoneMask) | (rdiv(r.x) & kZoneMask);
-    v.y = (L0 + (r.y & kZoneMask)) * c_eng.nranks + c_eng.rank;
+    v.x = (r.y & ~kZoneMask) | (slot_of(r.x) & kZoneMask);
+    v.y = global_of(L0 + (r.y & kZoneMask));
     v.z = r.z;
     v.w = r.w;
     st16(reinterpret_cast<uint4*>(c_eng.land[nxt] + ((d & ~kDirect) + rel)), v);
@@ -1601,7 +1601,7 @@ __device__ __forceinline__ bool zone_step(const uint32_t z, uint32_t cur, uint32
   const uint32_t nxt = cur ^ 1u;
   const uint32_t L0 = z * kZone;
   const uint32_t nact = min(kZone, c_eng.n_local - L0);
-  const uint32_t R = c_eng.nranks, me = c_eng.rank;
+  const uint32_t R = c_eng.nranks;
   const uint32_t nz = c_eng.n_zones;
   const uint32_t nb = nz + (R > 1 ? R : 0u);
   // The zone's offset, capacity and counters through SGPRs (zone_cap_s):
@@ -1680,7 +1680,7 @@ __device__ __forceinline__ bool zone_step(const uint32_t z, uint32_t cur, uint32
     if(tid == 0) c_eng.carry_n[nxt][z] = 0;
     if(ztn)
     {
-      for(uint32_t i = tid; i < nact; i += kZoneThreads) tb_out[(L0 + i) * R + me] = 0;
+      for(uint32_t i = tid; i < nact; i += kZoneThreads) tb_out[global_of(L0 + i)] = 0;
       if(tid == 0) c_eng.ztrig[nxt][z] = 0;
     }
     return false;
@@ -1690,7 +1690,7 @@ __device__ __forceinline__ bool zone_step(const uint32_t z, uint32_t cur, uint32
   // the trigger bytes of this zone's actors as the last step left them
   if(ztc)
     for(uint32_t i = tid; i < kZone; i += kZoneThreads)
-      s_tb[i] = i < nact ? c_eng.trig[cur][(L0 + i) * R + me] : (uint8_t)0;
+      s_tb[i] = i < nact ? c_eng.trig[cur][global_of(L0 + i)] : (uint8_t)0;
   else
     for(uint32_t i = tid; i < kZone / 4; i += kZoneThreads)
       reinterpret_cast<uint32_t*>(s_tb)[i] = 0;
@@ -1814,7 +1814,7 @@ __device__ __forceinline__ bool zone_step(const uint32_t z, uint32_t cur, uint32
         const uint32_t rd = act / kZoneThreads;               // its drain round
         pc.rh = s_hist + (rd >> 1) * nb;
         pc.inc = (rd & 1u) ? 0x10000u : 1u;
-        pc.self = (L0 + act) * R + me;
+        pc.self = global_of(L0 + act);
         pc.li = L0 + act - T.lfirst;
         pc.src_local = act;
         uint64_t junk[HT_Words<HTS>::W] = {};
@@ -2229,7 +2229,7 @@ __device__ __forceinline__ bool zone_step(const uint32_t z, uint32_t cur, uint32
         PlanCtx pc;
         pc.reset_common();
         pc.li = L0 + i - T.lfirst;
-        pc.self = (L0 + i) * R + me;
+        pc.self = global_of(L0 + i);
         pc.src_local = i;
         pc.type = tz;
         pc.rh = s_rh;
@@ -2285,7 +2285,7 @@ __device__ __forceinline__ bool zone_step(const uint32_t z, uint32_t cur, uint32
             const uint32_t i = ai[r];
             const uint32_t L = L0 + i;
             tc.li = L - T.lfirst;
-            tc.self = L * R + me;
+            tc.self = global_of(L);
             tc.src_local = i;
             tc.seq = 0;
             for(uint32_t j = 0; j < nm[r]; ++j) handle(HtTag<HTS>{}, T, tc, st[r], 0u, 0ull);
@@ -2432,7 +2432,7 @@ __device__ __forceinline__ bool zone_step(const uint32_t z, uint32_t cur, uint32
           const uint32_t i = r * kZoneThreads + tid;
           const uint32_t L = L0 + i;
           tc.li = L - T.lfirst;
-          tc.self = L * R + me;
+          tc.self = global_of(L);
           tc.src_local = i;
           tc.seq = 0;
           const uint32_t d = drain_commutative<HTS>(T, tc,
@@ -2544,7 +2544,7 @@ __device__ __forceinline__ bool zone_step(const uint32_t z, uint32_t cur, uint32
     const uint32_t n = s_cnt[i];
     const uint32_t L = L0 + i;
     a.li = L - T.lfirst;
-    a.self = L * R + me;
+    a.self = global_of(L);
     a.src_local = i;
     a.type = t;
     a.seq = 0;
@@ -2767,7 +2767,7 @@ __device__ __forceinline__ bool zone_step(const uint32_t z, uint32_t cur, uint32
           reinterpret_cast<uint32_t*>(tb_out + L0)[i] = reinterpret_cast<const uint32_t*>(s_tb)[i];
       }
     else
-      for(uint32_t i = tid; i < nact; i += kZoneThreads) tb_out[(L0 + i) * R + me] = s_tb[i];
+      for(uint32_t i = tid; i < nact; i += kZoneThreads) tb_out[global_of(L0 + i)] = s_tb[i];
     if(tid == 0)
     {
       c_eng.ztrig[nxt][z] = ntrig;
@@ -2999,7 +2999,7 @@ __device__ __forceinline__ void land_records(LandRec (&r)[kLandPer], uint32_t cu
   for(int u = 0; u < kLandPer; ++u)
     if(r[u].valid)
     {
-      zt[u] = zone_of_local(rdiv(r[u].to));
+      zt[u] = zone_of_local(slot_of(r[u].to));
       rk[u] = atomicAdd(&s_hist[zt[u]], 1u);
     }
   __syncthreads();
@@ -3012,7 +3012,7 @@ __device__ __forceinline__ void land_records(LandRec (&r)[kLandPer], uint32_t cu
     {
       const uint32_t pos = s_base[zt[u]] + rk[u];
       uint4 v;
-      v.x = r[u].w | slot_in_zone(rdiv(r[u].to));
+      v.x = r[u].w | slot_in_zone(slot_of(r[u].to));
       v.y = r[u].from;
       v.z = (uint32_t)r[u].arg;
       v.w = (uint32_t)(r[u].arg >> 32);
@@ -3073,7 +3073,7 @@ __global__ void __launch_bounds__(kLandThreads) k_xinject(const XRec* in, uint64
   __shared__ uint32_t s_base[kMaxZones];
   __shared__ unsigned long long s_app[GPU_ACTOR_MAX_TYPES];
   __shared__ unsigned long long s_roff[kMaxRanks];
-  const uint32_t R = c_eng.nranks, me = c_eng.rank;
+  const uint32_t R = c_eng.nranks;
   if(threadIdx.x < GPU_ACTOR_MAX_TYPES) s_app[threadIdx.x] = 0;
   if(threadIdx.x == 0)
   {
@@ -3099,7 +3099,7 @@ __global__ void __launch_bounds__(kLandThreads) k_xinject(const XRec* in, uint64
       const XRec x = stride ? xrec_get(in + src * stride + (i - s_roff[src])) : in[i];
       const uint32_t seq = (x.w0 >> 27) << 9 | (x.w1 >> 23);
       const uint32_t beh = (x.w0 >> 23) & 0xFu;
-      const uint32_t to = (x.w0 & 0x7FFFFFu) * R + me;
+      const uint32_t to = global_of(x.w0 & 0x7FFFFFu);
       if(seq == kXSeqApply)
       {
         reducible_apply_local(to, beh, x.arg);
@@ -3111,7 +3111,7 @@ __global__ void __launch_bounds__(kLandThreads) k_xinject(const XRec* in, uint64
         r[u].valid = true;
         r[u].to = to;
         r[u].w = seq << 16 | beh << 12;
-        r[u].from = (x.w1 & 0x7FFFFFu) * R + src;
+        r[u].from = global_on(src, x.w1 & 0x7FFFFFu);
         r[u].arg = x.arg;
       }
     }

@@ -11,13 +11,16 @@ Two exchanges are available to an engine with n_ranks > 1:
   several processes sharing ONE GPU (the test box has one), and on hosts
   without xGMI peers.  It is not a fast path.
 
-Actor `id` lives on rank `id % n_ranks` (`gpu_actor_owner`).
+Actor `id` lives on rank `Engine.owner_of(id)` (`gpu_actor_owner`): `id % n_ranks`
+by default, block `(id >> b) % n_ranks` with `Engine(block_bits=b)`.
 """
 from __future__ import annotations
 
 import numpy as np
 import torch
 import torch.distributed as dist
+
+from .engine import place_owner
 
 
 class GlooTransport:
@@ -62,11 +65,13 @@ def gather_state(eng, type_id: int, group=None) -> np.ndarray:
     local = eng.state_read(type_id)
     parts = [None] * dist.get_world_size(group)
     dist.all_gather_object(parts, (eng.rank, local), group=group)
-    first, count, n = eng.first[type_id], eng.count[type_id], eng.n_ranks
+    first, count = eng.first[type_id], eng.count[type_id]
     out = np.zeros((eng.words[type_id], count), dtype=np.uint64)
     ids = np.arange(first, first + count, dtype=np.int64)
+    # (Engine.owner_of's map; an engine-like object without a placement has the default)
+    owner = place_owner(eng.n_ranks, getattr(eng, "block_bits", 0), ids)
     for r, st in parts:
-        mine = ids[ids % n == r] - first
+        mine = ids[owner == r] - first
         out[:, mine] = st
     return out
 

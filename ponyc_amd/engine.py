@@ -102,6 +102,13 @@ HOST_EXPORTS = [
 # (include/gpu_actor_host.h: gpu_actor_host_fn)
 HOST_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64)
 
+# actor placement (include/gpu_actor_place.h): every symbol that header declares
+PLACE_MAX_BITS = 16
+PLACE_EXPORTS = [
+    "gpu_actor_place_blocks", "gpu_actor_place_map", "gpu_actor_place_global",
+    "gpu_actor_place_below",
+]
+
 # host-transport callbacks (include/gpu_actor.h: gpu_actor_alltoallv_fn / _allreduce_fn)
 ALLTOALLV_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                 ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p,
@@ -161,6 +168,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "gpu_actor_recv": (i32, [vp, u64, ctypes.POINTER(u64)]),
         "gpu_actor_recv_pending": (i32, [ctypes.POINTER(u64)]),
         "gpu_actor_host_notify": (i32, [HOST_FN, vp]),
+        # include/gpu_actor_place.h
+        "gpu_actor_place_blocks": (i32, [u32]),
+        "gpu_actor_place_map": (i32, [u32, u32, u64, ctypes.POINTER(u32), ctypes.POINTER(u64)]),
+        "gpu_actor_place_global": (i32, [u32, u32, u32, u64, ctypes.POINTER(u64)]),
+        "gpu_actor_place_below": (i32, [u32, u32, u32, u64, ctypes.POINTER(u64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -205,6 +217,27 @@ def _ck(fn: str, rc: int) -> None:
         raise GpuActorError(fn, rc)
 
 
+# -- placement (include/gpu_actor_place.h), vectorised over numpy arrays ---------
+def place_owner(n_ranks: int, block_bits: int, ids) -> np.ndarray:
+    """Rank of each id: block (id >> b) % R."""
+    ids = np.asarray(ids, dtype=np.uint64)
+    return ((ids >> np.uint64(block_bits)) % np.uint64(n_ranks)).astype(np.uint32)
+
+
+def place_slot(n_ranks: int, block_bits: int, ids) -> np.ndarray:
+    """Local slot of each id on its owner: ((id >> b) / R) << b | id & (2^b - 1)."""
+    ids = np.asarray(ids, dtype=np.uint64)
+    b = np.uint64(block_bits)
+    return (((ids >> b) // np.uint64(n_ranks)) << b) | (ids & np.uint64((1 << block_bits) - 1))
+
+
+def place_below(n_ranks: int, block_bits: int, rank: int, x: int) -> int:
+    """Ids below x that `rank` owns: where a type created at id x starts there."""
+    f, size = x >> block_bits, 1 << block_bits
+    whole = (f - rank + n_ranks - 1) // n_ranks if f > rank else 0
+    return size * whole + ((x & (size - 1)) if f % n_ranks == rank else 0)
+
+
 def as_msgs(msgs) -> np.ndarray:
     """Accept a MSG_DTYPE array or an iterable of (to, behaviour, arg)."""
     if isinstance(msgs, np.ndarray) and msgs.dtype == MSG_DTYPE:
@@ -219,12 +252,20 @@ class Engine:
 
     def __init__(self, device: int = 0, n_ranks: int = 1, rank: int = 0, batch: int = 0,
                  mailbox_cap: int = 0, max_actors: int = 0, max_exchange: int = 0,
-                 comm_id: bytes | None = None, transport=None):
+                 comm_id: bytes | None = None, transport=None, block_bits: int | None = None):
         """`comm_id` selects the RCCL exchange; `transport` (an object with
         `alltoallv(send, send_bytes, recv, recv_bytes)` and `allreduce(buf)`
         over numpy arrays, e.g. `ponyc_amd.dist.GlooTransport`) selects the
-        host-staged exchange instead. One of them is required when n_ranks > 1."""
+        host-staged exchange instead. One of them is required when n_ranks > 1.
+        `block_bits` = b places blocks of 2^b consecutive ids on one rank
+        (include/gpu_actor_place.h; every rank must pass the same value); None
+        is the default placement: PONYC_AMD_BLOCK_BITS, else id % n_ranks."""
         self.lib = load_library()
+        # (the library keeps the last choice for later sessions: every Engine sets its own)
+        if block_bits is None:
+            block_bits = int(os.environ.get("PONYC_AMD_BLOCK_BITS") or 0)
+        _ck("gpu_actor_place_blocks", self.lib.gpu_actor_place_blocks(block_bits))
+        self.block_bits = block_bits
         self._xp = None
         if transport is not None:
             self._xp = _wrap_transport(transport)
@@ -356,12 +397,22 @@ class Engine:
 
     # -- state / counters ----------------------------------------------------------
     def local_count(self, type_id: int) -> int:
-        """Actors of a type owned by this rank (ids first + k*n_ranks + ...)."""
-        first, count, r, n = self.first[type_id], self.count[type_id], self.rank, self.n_ranks
+        """Actors of a type owned by this rank (of ids first .. first + count)."""
+        first, count = self.first[type_id], self.count[type_id]
+        return self.below(first + count) - self.below(first)
 
-        def below(x):
-            return (x - r + n - 1) // n if x > r else 0
-        return below(first + count) - below(first)
+    # -- placement (include/gpu_actor_place.h) -----------------------------------
+    def owner_of(self, ids) -> np.ndarray:
+        """Rank that owns each id under this engine's placement."""
+        return place_owner(self.n_ranks, self.block_bits, ids)
+
+    def slot_of(self, ids) -> np.ndarray:
+        """Local slot of each id on its owner: dense and increasing in id."""
+        return place_slot(self.n_ranks, self.block_bits, ids)
+
+    def below(self, x: int, rank: int | None = None) -> int:
+        """Ids below x owned by `rank` (default: this rank)."""
+        return place_below(self.n_ranks, self.block_bits, self.rank if rank is None else rank, x)
 
     def state_read(self, type_id: int, first: int = 0, n: int | None = None) -> np.ndarray:
         """Field-major state: out[w, i] = word w of local actor first+i."""
@@ -440,7 +491,7 @@ class Engine:
                 "trig_n0", "trig_n1", "trig_n2", "zone_bits", "hot_missed", "hot_on", "jit",
                 "jit_builds", "gups_updates", "gups_atomics", "peer_write",
                 "gups_chunks_in", "gups_chunks_out", "gups_remote", "plan_zones",
-                "land8_records"]
+                "land8_records", "block_bits"]
         out = (ctypes.c_uint64 * len(keys))()
         fn = self.lib.gpu_actor_debug_info
         fn.argtypes = [ctypes.c_void_p, ctypes.c_uint64]

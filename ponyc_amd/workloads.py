@@ -30,17 +30,17 @@ def _msgs(to, beh, arg) -> np.ndarray:
 
 def _sendv(eng, m: np.ndarray) -> None:
     """Each rank runs the same Main and injects its own share: the messages
-    addressed to actors it owns (id % n_ranks == rank); the C-ABI rejects the
+    addressed to actors it owns (Engine.owner_of); the C-ABI rejects the
     others (include/gpu_actor.h, gpu_actor_sendv)."""
     r = getattr(eng, "n_ranks", 1)
     if r > 1:
-        m = m[(m["to"].astype(np.uint64) % np.uint64(r)) == np.uint64(eng.rank)]
+        m = m[eng.owner_of(m["to"]) == eng.rank]
     eng.sendv(m)
 
 
 def _send(eng, to: int, beh: int, arg: int) -> None:
     r = getattr(eng, "n_ranks", 1)
-    if r == 1 or to % r == eng.rank:
+    if r == 1 or int(eng.owner_of(to)) == eng.rank:
         eng.send(to, beh, arg)
 
 
@@ -82,10 +82,10 @@ def ring_prog(eng, size: int, count: int, passes: int, type_id: int = 0) -> dict
     st[0] = np.where(pos == 0, np.uint64(NONE_ID),
                      np.uint64(first) + ring_i * np.uint64(size) + (pos + np.uint64(1)) % np.uint64(size))
     st[1] = pos + np.uint64(1)
-    # each rank writes the actors it owns (id % n_ranks == rank), in id order
+    # each rank writes the actors it owns (Engine.owner_of), in id order
     r = getattr(eng, "n_ranks", 1)
     if r > 1:
-        st = st[:, ((np.uint64(first) + i) % np.uint64(r)) == np.uint64(eng.rank)]
+        st = st[:, eng.owner_of(np.uint64(first) + i) == eng.rank]
     eng.state_write(type_id, st)
     heads = first + np.arange(count, dtype=np.uint64) * np.uint64(size)
     m = np.empty(2 * count, dtype=MSG_DTYPE)
