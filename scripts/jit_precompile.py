@@ -40,6 +40,10 @@ def sets():
     # the conformance sets (tests/prog_conformance.py): three program sets and
     # the ring + program mix, at both geometries
     out += jit_units()
+    # the mixed worlds that run with the JIT on (tests/mixed_worlds.py), at
+    # both geometries
+    from mixed_worlds import mix_units
+    out += mix_units()
     return out
 
 
