@@ -201,6 +201,46 @@ def emitter_program(ports_param: int = 0, n_ports_param: int = 1, magic_param: i
     return p.assemble()
 
 
+def fold_program() -> np.ndarray:
+    """An order-sensitive receiver (the FIFO probe's sink without its
+    per-sender counters; tests/host_order.py). Behaviour 0: word 0 h = (h ^
+    arg) * 0x100000001b3, from 0; word 1 the messages."""
+    p = Program()
+    p.behaviour(0)
+    p.addi(1, 1, 1)
+    p.xor(0, 0, R_ARG)
+    p.ldi(14, 1)
+    p.ldi(15, 40)
+    p.shl(14, 14, 15)
+    p.addi(14, 14, 0x1b3)               # the FNV prime
+    p.mul(0, 0, 14)
+    p.halt()
+    return p.assemble()
+
+
+def burst_program() -> np.ndarray:
+    """The FIFO probe's source for fold_program sinks. Behaviour 0 BURST(m):
+    m times, bump c (word 1) and SEND behaviour 0 with index << 32 | c to the
+    sink in word 0 (written by the host); index = self - param 0."""
+    p = Program()
+    p.behaviour(0)
+    p.ldp(11, 0)
+    p.sub(11, R_SELF, 11)
+    p.ldi(12, 32)
+    p.shl(11, 11, 12)                   # index << 32
+    p.mov(12, R_ARG)                    # sends left
+    p.label("loop")
+    p.jz(12, "end")
+    p.addi(1, 1, 1)
+    p.or_(14, 11, 1)
+    p.send(0, 0, 14)
+    p.addi(12, 12, -1)
+    p.jmp("loop")
+    p.label("end")
+    p.halt()
+    return p.assemble()
+
+
 def spreader_program(type_id: int) -> np.ndarray:
     """examples/spreader/main.pony:1-48 (the compiled GPU_ACTOR_HT_SPREADER,
     engine_dev.h) for a program type `type_id`: word 0 count, 1 parent (~0:

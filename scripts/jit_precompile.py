@@ -30,6 +30,8 @@ def sets():
     # the all-program spawn world (tests/test_gpu_limits.py test_spawn_high_seq)
     from test_gpu_limits import spawn_programs
     out.append((spawn_programs(), False))
+    # the program sinks and sources of tests/test_gpu_host_order.py
+    out.append(([(0, P.fold_program()), (1, P.burst_program())], False))
     # any-mix engines of the tests (bit per table id): ring + FIFO source +
     # sink (test_hot_zones_past_kmaxhot), ring + spreader + fan-in sender
     # (test_spreader_after_other_types), FIFO sink + program

@@ -15,6 +15,7 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import numpy as np                       # noqa: E402
 import torch.distributed as dist         # noqa: E402
 
+import host_order as HO                  # noqa: E402
 from ponyc_amd import workloads as W     # noqa: E402
 from ponyc_amd.dist import GlooTransport, GlobalView   # noqa: E402
 from ponyc_amd.engine import Engine      # noqa: E402
@@ -72,6 +73,10 @@ CASES = {
     # behaviours as programs (GPU_ACTOR_HT_PROGRAM): sends across ranks
     "ring_prog": (lambda e: W.ring_prog(e, 64, 4, 100), lambda e, w: e.state_read(w["type"]), {}),
     "det_prog": (lambda e: W.det_prog(e, 3001, 3, hops=40), lambda e, w: e.state_read(w["type"]), {}),
+    # the host of each rank among the senders of ordered groups of 308 (tests/
+    # host_order.py two_ranks: the setup runs the first step and sends the
+    # host's window, so the oracle is driven the same way)
+    "host_order": (HO.two_ranks, W.fifo_result, {}),
 }
 
 

@@ -40,7 +40,7 @@ def test_host_plumbing_gloo(nproc):
 TWO_RANK_CASES = ["ring", "ring1", "ubench", "ubench_det", "fanin", "gups", "storm", "fifo",
                   "fifo_seq", "fifo_seq_max", "fifo_seq_max_carry", "spreader", "mute",
                   "priority", "spill", "spill_one_rank", "spill_one_rank_fixed", "xspill",
-                  "xspill_det", "backlog", "zones_edge", "ring_prog", "det_prog"]
+                  "xspill_det", "backlog", "zones_edge", "ring_prog", "det_prog", "host_order"]
 ZONES_4096_CASES = ["ubench_det", "storm", "fifo_seq_max", "spreader", "mute", "spill_one_rank",
                     "xspill", "backlog"]
 
