@@ -8,7 +8,6 @@
 // The launch boundary is the BSP barrier; quiescence ("no pending mail on any
 // rank") replaces the CNF/ACK protocol (scheduler.c:303-480).
 #include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
 #include <hipcub/hipcub.hpp>
 #include <rccl/rccl.h>
 
@@ -33,20 +32,6 @@
 #include "step_entry.h"
 #include "jit_host.h"
 #include "dev_buf.h"
-
-// the 4096-actor-zone instantiations (step_*_z12.hip)
-namespace gpa_z12 {
-StepEntry step_entry_any();
-StepEntry step_entry_ring();
-StepEntry step_entry_pinger();
-StepEntry step_entry_pinger_det();
-StepEntry step_entry_fanin_sender();
-StepEntry step_entry_gups_streamer();
-StepEntry step_entry_storm();
-StepEntry step_entry_spreader();
-StepEntry step_entry_fifo_pair();
-StepEntry step_entry_program();
-} // namespace gpa_z12
 
 using namespace gpa;
 
@@ -442,6 +427,28 @@ struct Process {
   int place_bits = -1;
 };
 
+// What a superstep launches, decided once per configuration (types, programs,
+// geometry, zones, ranks, environment knobs) by plan_step() at every constants
+// upload, which each change of the configuration ends in; launch_step reads it.
+struct StepPlan {
+  StepEntry entry{};                    // the compiled-in step of the engine's tables
+  // a stub: an experiment build without this table (GPU_ACTOR_EINVAL); fits:
+  // static LDS + dyn within a workgroup's LDS (GPU_ACTOR_ERANGE otherwise)
+  bool stub = false, fits = false;
+  size_t dyn = 0;                       // dynamic LDS of each k_step launch
+  // the compiled-in launches: the whole step (PM 0), or a split table's as
+  // one launch (PM 3: first) or two (PM 1: first, PM 2: second)
+  step_kernel_t first = nullptr, second = nullptr;
+  // the run-time compiled step taken instead where it builds and fits
+  // (jit_host.h): 0 none, 1 the programs', 2 the any-mix step of the tables
+  // in jit_mask; jit_key names the module. Built or loaded at the first
+  // launch (jit_ready), whose answer stands for this plan.
+  int jit_kind = 0;
+  uint32_t jit_mask = 0;
+  uint64_t jit_key = 0;
+  bool jit_asked = false, jit_ok = false;
+};
+
 // One engine, from gpu_actor_init to gpu_actor_shutdown (or to a failed init):
 // every field starts from its initialiser here, the buffers free themselves
 // (dev_buf.h), and session_end() replaces the whole value — nothing below is
@@ -571,13 +578,10 @@ struct Session {
   DevBuf<uint32_t> d_muted_on;
   DevBuf<uint32_t> d_ztrig[2];
   DevBuf<unsigned int> d_trig_n;
-  // zones the step's two-pass launch ran (EngDev::zplan); split_plan: run a
-  // two-pass table's step as the two launches (PONYC_AMD_SPLIT_PLAN=0: one)
+  // zones the step's two-pass launch ran (EngDev::zplan)
   DevBuf<uint32_t> d_zplan;
-  bool split_plan = true;
-  // split tables: the step as one launch (k_step PM 3: the rest through a
-  // call) instead of two (PONYC_AMD_FUSE=0: two)
-  bool fuse = true;
+  // what a step launches in this configuration (plan_step, from upload_types)
+  StepPlan plan;
   uint32_t sidx = 0;
   // backlog copies handed to k_carry_big (EngDev::bigc)
   DevBuf<BigCopy> d_bigc;
@@ -712,18 +716,88 @@ inline bool reducible_ht(uint32_t ht)
          ht == GPU_ACTOR_HT_HOST_PORT;
 }
 
-const std::vector<StepEntry>& step_entries()
+// The compiled steps (step_entry.h GPA_STEP_TABLES): a row per table, its
+// entry at each zone geometry.
+struct StepRow {
+  int ht;
+  StepEntry geo[2];        // [0]: 2048-actor zones, [1]: 4096-actor zones
+};
+// the handler tables of the engine's serial actors, a bit per table id
+uint32_t serial_tables()
 {
-  static const std::vector<StepEntry> v = {
-    gpa::step_entry_any(), gpa::step_entry_ring(), gpa::step_entry_pinger(),
-    gpa::step_entry_pinger_det(), gpa::step_entry_fanin_sender(),
-    gpa::step_entry_gups_streamer(), gpa::step_entry_storm(), gpa::step_entry_spreader(),
-    gpa_z12::step_entry_any(), gpa_z12::step_entry_ring(), gpa_z12::step_entry_pinger(),
-    gpa_z12::step_entry_pinger_det(), gpa_z12::step_entry_fanin_sender(),
-    gpa_z12::step_entry_gups_streamer(), gpa_z12::step_entry_storm(),
-    gpa_z12::step_entry_spreader(), gpa::step_entry_fifo_pair(), gpa_z12::step_entry_fifo_pair(),
-    gpa::step_entry_program(), gpa_z12::step_entry_program()};
+  uint32_t set = 0;
+  for(const HostType& t : g.types)
+    if(t.created && !reducible_ht(t.ht)) set |= 1u << t.ht;
+  return set;
+}
+
+const std::vector<StepRow>& step_rows()
+{
+  static const std::vector<StepRow> v = {
+#define GPA_STEP_X(name, ht) {ht, {gpa::step_entry_##name(), gpa_z12::step_entry_##name()}},
+    GPA_STEP_TABLES(GPA_STEP_X)
+#undef GPA_STEP_X
+  };
   return v;
+}
+
+// The step of handler table ht (kHtFifoPair: the FIFO pair; -1, and every
+// table without a step of its own: the any-mix step) at a geometry.
+const StepEntry& step_entry(int ht, bool z12)
+{
+  const StepEntry* any = nullptr;
+  for(const StepRow& r : step_rows())
+  {
+    if(r.ht == ht) return r.geo[z12];
+    if(r.ht == -1) any = &r.geo[z12];
+  }
+  return *any;
+}
+
+// k_step compiled for the one handler table all serial actors share, when
+// they do (smaller code, no spills); the any-mix instantiation otherwise.
+StepEntry step_entry_for(bool z12)
+{
+  const uint32_t set = serial_tables();
+  // the FIFO pair's rule comes first: sources and sinks, and nothing else
+  if(set == ((1u << GPU_ACTOR_HT_FIFO_SRC) | (1u << GPU_ACTOR_HT_FIFO_SINK)))
+    return step_entry(kHtFifoPair, z12);
+  return step_entry(set && !(set & (set - 1)) ? __builtin_ctz(set) : -1, z12);
+}
+
+StepEntry pick_step_entry() { return step_entry_for(g.zbits == 12); }
+
+// LDS a workgroup may hold on gfx950 (the CU's whole 160 KB; two 512-thread
+// zones per CU at <= 80 KB each)
+constexpr size_t kLdsPerWorkgroup = 160 * 1024;
+
+// Dynamic LDS of a step launch with nb destination buckets: the bucket
+// arrays (zone_dev.h: histogram, chunk bases, tile counts, tile starts, and
+// the two-pass table's round counts) or the hot-group sort's work area.
+size_t step_dyn_bytes(const StepEntry& se, uint64_t nb)
+{
+  return sizeof(uint32_t) * std::max<uint64_t>((uint64_t)se.bucket_words * nb, se.sort_work);
+}
+
+// Whether a step launch with nb buckets fits a workgroup's LDS: static LDS of
+// every kernel of the entry (hipFuncGetAttributes) + the dynamic part.
+bool step_fits(const StepEntry& se, uint64_t nb)
+{
+  static std::map<step_kernel_t, size_t> cache;     // (callers hold gp.mu)
+  size_t st = 0;
+  for(step_kernel_t k : {se.kernel, se.plan, se.rest, se.fused})
+  {
+    if(!k) continue;
+    auto it = cache.find(k);
+    if(it == cache.end())
+    {
+      hipFuncAttributes a;
+      if(hipFuncGetAttributes(&a, reinterpret_cast<const void*>(k)) != hipSuccess) return false;
+      it = cache.emplace(k, a.sharedSizeBytes).first;
+    }
+    st = std::max<size_t>(st, it->second);
+  }
+  return st + step_dyn_bytes(se, nb) <= kLdsPerWorkgroup;
 }
 
 // Backlog copies go to k_carry_big (the whole GPU copies them right after
@@ -736,17 +810,9 @@ const std::vector<StepEntry>& step_entries()
 bool defer_big_wanted()
 {
   if(const char* f = getenv("PONYC_AMD_DEFER_BIG")) return atoi(f) != 0;
-  int only = -1;
-  for(const HostType& t : g.types)
-  {
-    if(!t.created || reducible_ht(t.ht)) continue;
-    if(only >= 0 && (uint32_t)only != t.ht) return true;
-    only = (int)t.ht;
-  }
-  return false;
+  const uint32_t set = serial_tables();
+  return (set & (set - 1)) != 0;
 }
-
-StepEntry pick_step_entry();
 
 inline uint32_t* hot_bar_words() { return g.d_hot + kHotLayout.bar; }
 
@@ -851,22 +917,22 @@ int gups_setup(EngDev& e)
 
 // k_gups_apply behind a step's kernels (engines with a chunk-listing streamer
 // type, one rank; with more the chunks are applied after the exchange,
-// gups_gather_apply); the events, when given, end at its end
-int gups_apply_launch(hipEvent_t e1)
+// gups_gather_apply)
+int gups_apply_launch()
 {
   if(g.gups_type < 0 || R() > 1) return 0;
-  if(e1)
-    hipExtLaunchKernelGGL(k_gups_apply, dim3(kGupsBlocks), dim3(256), 0, g.stream, nullptr, e1, 0u);
-  else
-    hipLaunchKernelGGL(k_gups_apply, dim3(kGupsBlocks), dim3(256), 0, g.stream);
+  hipLaunchKernelGGL(k_gups_apply, dim3(kGupsBlocks), dim3(256), 0, g.stream);
   HIPCK(hipGetLastError());
   return 0;
 }
 
 bool land8_table();
+void plan_step(const StepEntry& se);
 
 int upload_types()
 {
+  const StepEntry se = pick_step_entry();
+  plan_step(se);
   TypeDev td[GPU_ACTOR_MAX_TYPES];
   memset(td, 0, sizeof(td));
   for(uint32_t t = 0; t < GPU_ACTOR_MAX_TYPES; ++t)
@@ -935,7 +1001,7 @@ int upload_types()
   e.block_bits = g.block_bits;
   {
     g.land8 = land8_table() && g.d_landc[0] && g.d_landc[1] && g.d_sstat;
-    if(g.land8) g.land8_arg = pick_step_entry().plan_arg;
+    if(g.land8) g.land8_arg = se.plan_arg;
     e.land8 = g.land8 ? 1u : 0u;
     for(int p = 0; p < 2; ++p) { e.landc[p] = g.d_landc[p]; e.landc_n[p] = g.d_landc_n[p]; }
     e.lc_over = g.d_sstat ? &g.d_sstat->lc_over : nullptr;
@@ -947,7 +1013,7 @@ int upload_types()
   // phases meet at grid barriers.
   {
     const char* f = getenv("PONYC_AMD_HOT");
-    g.hot_on = pick_step_entry().hot && (f ? atoi(f) != 0 : g.defer_big) && hot_resident();
+    g.hot_on = se.hot && (f ? atoi(f) != 0 : g.defer_big) && hot_resident();
     e.hot_on = g.hot_on ? 1u : 0u;
     const char* t = getenv("PONYC_AMD_HOT_TEST");
     e.hot_test = (t && atoi(t) != 0) ? 1u : 0u;
@@ -957,10 +1023,6 @@ int upload_types()
   {
     const char* f = getenv("PONYC_AMD_TWO_PASS");
     e.two_pass = (f && atoi(f) == 0) ? 0u : 1u;
-    const char* sp = getenv("PONYC_AMD_SPLIT_PLAN");
-    g.split_plan = !(sp && atoi(sp) == 0);
-    const char* fu = getenv("PONYC_AMD_FUSE");
-    g.fuse = !(fu && atoi(fu) == 0);
   }
   e.zplan = g.d_zplan;
   if(g.host_ports && g.host_seg)     // (host_seg 0: the lists could not be allocated)
@@ -990,8 +1052,9 @@ int upload_types()
   HIPCK(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_eng), &e, sizeof(e), 0,
     hipMemcpyHostToDevice, g.stream));
   // every k_step code object holds its own copy of the constants
-  for(const StepEntry& se : step_entries())
-    HIPCK(se.upload(td, &e, g.stream));
+  for(const StepRow& r : step_rows())
+    for(const StepEntry& u : r.geo)
+      HIPCK(u.upload(td, &e, g.stream));
   memcpy(g.td_host, td, sizeof(td));
   g.eng_host = e;
   g.consts_host = true;
@@ -1017,10 +1080,6 @@ int ensure_spill(uint64_t cap)
 
 int relayout_zones(bool geometry = false);
 int land8_flush();
-bool land8_table();
-StepEntry step_entry_for(bool z12);
-bool step_fits(const StepEntry& se, uint64_t nb);
-int upload_types();
 int pend_read(uint32_t first, uint32_t n, std::vector<unsigned long long>& out);
 
 // Spill list length for the current zone layout: a quarter of its records.
@@ -2163,76 +2222,6 @@ int exchange_step(uint32_t step_sidx)
   return xc_allreduce_sum(g.d_spill_flag, g.d_spill_flag, 1, XC_U32);
 }
 
-// k_step compiled for the one handler table all serial actors share, when
-// they do (smaller code, no spills); the any-mix instantiation otherwise.
-StepEntry step_entry_for(bool z12)
-{
-  int only = -1;
-  bool mixed = false;
-  uint32_t set = 0;                     // tables of the serial actors, as bits
-  for(const HostType& t : g.types)
-  {
-    if(!t.created || reducible_ht(t.ht)) continue;
-    if(only >= 0 && (uint32_t)only != t.ht) mixed = true;
-    only = (int)t.ht;
-    set |= 1u << t.ht;
-  }
-  if(mixed) only = -1;
-  if(set == ((1u << GPU_ACTOR_HT_FIFO_SRC) | (1u << GPU_ACTOR_HT_FIFO_SINK)))
-    return z12 ? gpa_z12::step_entry_fifo_pair() : gpa::step_entry_fifo_pair();
-  switch(only)
-  {
-    case GPU_ACTOR_HT_RING: return z12 ? gpa_z12::step_entry_ring() : gpa::step_entry_ring();
-    case GPU_ACTOR_HT_PINGER: return z12 ? gpa_z12::step_entry_pinger() : gpa::step_entry_pinger();
-    case GPU_ACTOR_HT_PINGER_DET:
-      return z12 ? gpa_z12::step_entry_pinger_det() : gpa::step_entry_pinger_det();
-    case GPU_ACTOR_HT_FANIN_SENDER:
-      return z12 ? gpa_z12::step_entry_fanin_sender() : gpa::step_entry_fanin_sender();
-    case GPU_ACTOR_HT_GUPS_STREAMER:
-      return z12 ? gpa_z12::step_entry_gups_streamer() : gpa::step_entry_gups_streamer();
-    case GPU_ACTOR_HT_STORM: return z12 ? gpa_z12::step_entry_storm() : gpa::step_entry_storm();
-    case GPU_ACTOR_HT_SPREADER: return z12 ? gpa_z12::step_entry_spreader() : gpa::step_entry_spreader();
-    case GPU_ACTOR_HT_PROGRAM: return z12 ? gpa_z12::step_entry_program() : gpa::step_entry_program();
-    default: return z12 ? gpa_z12::step_entry_any() : gpa::step_entry_any();
-  }
-}
-
-StepEntry pick_step_entry() { return step_entry_for(g.zbits == 12); }
-StepEntry step_entry_for_any(bool z12) { return z12 ? gpa_z12::step_entry_any() : gpa::step_entry_any(); }
-
-// LDS a workgroup may hold on gfx950 (the CU's whole 160 KB; two 512-thread
-// zones per CU at <= 80 KB each)
-constexpr size_t kLdsPerWorkgroup = 160 * 1024;
-
-// Dynamic LDS of a step launch with nb destination buckets: the bucket
-// arrays (zone_dev.h: histogram, chunk bases, tile counts, tile starts, and
-// the two-pass table's round counts) or the hot-group sort's work area.
-size_t step_dyn_bytes(const StepEntry& se, uint64_t nb)
-{
-  return sizeof(uint32_t) * std::max<uint64_t>((uint64_t)se.bucket_words * nb, se.sort_work);
-}
-
-// Whether a step launch with nb buckets fits a workgroup's LDS: static LDS of
-// every kernel of the entry (hipFuncGetAttributes) + the dynamic part.
-bool step_fits(const StepEntry& se, uint64_t nb)
-{
-  static std::map<step_kernel_t, size_t> cache;     // (callers hold gp.mu)
-  size_t st = 0;
-  for(step_kernel_t k : {se.kernel, se.plan, se.rest, se.fused})
-  {
-    if(!k) continue;
-    auto it = cache.find(k);
-    if(it == cache.end())
-    {
-      hipFuncAttributes a;
-      if(hipFuncGetAttributes(&a, reinterpret_cast<const void*>(k)) != hipSuccess) return false;
-      it = cache.emplace(k, a.sharedSizeBytes).first;
-    }
-    st = std::max<size_t>(st, it->second);
-  }
-  return st + step_dyn_bytes(se, nb) <= kLdsPerWorkgroup;
-}
-
 // Ids and landing for the actors the last step's behaviours created: the
 // records are sorted by (type, creator, seq) — the canonical order — and
 // numbered after each type's live actors (k_spawn_*). One small readback per
@@ -2448,91 +2437,137 @@ int host_collect()
   return 0;
 }
 
-// One superstep: k_step on parity g.par (+ exchange), then flip parity.
-// The run-time compiled step this engine's tables take (jit_host.h), built
-// or loaded once per set (a set whose build fails stays on the compiled-in
-// kernels; one seen before in this process, or on disk, loads at once), with
-// PONYC_AMD_JIT not 0: 1 — every serial actor runs a program: the programs
-// compiled (two launches, PM 1 plain zones and PM 2 the rest, with the split
-// launches on); 2 — a mix of tables the any-mix kernel would run: that
-// kernel with only those tables' drains; 0 — neither.
-int step_after_launch(uint32_t slot, hipEvent_t e0, hipEvent_t e1);
-int jit_ensure(const StepEntry& se)
+// The plan of a step (StepPlan) for the configuration as it stands: the
+// compiled-in entry `se` and its launch form, and the run-time compiled step
+// it takes instead (jit_host.h), with PONYC_AMD_JIT not 0: 1 — every serial
+// actor runs a program: the programs compiled (two launches, PM 1 plain zones
+// and PM 2 the rest, with the split launches on); 2 — a mix of tables the
+// any-mix kernel would run: that kernel with only those tables' drains;
+// 0 — neither. The environment knobs are read here, once per configuration.
+void plan_step(const StepEntry& se)
 {
+  StepPlan p;
+  p.entry = se;
+  p.stub = se.stub;
+  // bucket arrays (4 x buckets — an order-free zone's two passes need no
+  // more: zone_dev.h two_pass; six for a message-local table's, dp_table)
+  // and, for hot receivers, the sort's work area
+  const uint64_t nb = g.n_zones + (R() > 1 ? R() : 0);
+  p.fits = step_fits(se, nb);
+  p.dyn = step_dyn_bytes(se, nb);
+  // a two-pass table's step as two launches: its two-pass zones, then the
+  // rest (zone_dev.h k_step PM; PONYC_AMD_SPLIT_PLAN=0: one launch of the
+  // whole), or fused: one launch of PM 3 in their place (PONYC_AMD_FUSE=0: two)
+  const char* sp = getenv("PONYC_AMD_SPLIT_PLAN");
+  const char* fu = getenv("PONYC_AMD_FUSE");
+  const bool split_plan = !(sp && atoi(sp) == 0);
+  const bool fused = se.plan && split_plan && !(fu && atoi(fu) == 0) && se.fused;
+  const bool split = se.plan && split_plan && !fused;
+  p.first = fused ? se.fused : split ? se.plan : se.kernel;
+  p.second = split ? se.rest : nullptr;
+  g.plan = p;
   const char* f = getenv("PONYC_AMD_JIT");
-  if((f && atoi(f) == 0) || !g.consts_host) return 0;
+  if(f && atoi(f) == 0) return;
   const bool z12 = g.zbits == 12;
-  std::vector<jit::Prog> progs;
-  uint32_t mask = 0;
-  bool all_prog = true;
-  for(uint32_t t = 0; t < GPU_ACTOR_MAX_TYPES; ++t)
+  const uint64_t geo = jit::fnv1a(z12 ? "z12" : "z11");
+  uint64_t key = geo;                   // of the programs, while every serial type has one
+  p.jit_mask = serial_tables();
+  bool all_prog = p.jit_mask == 1u << GPU_ACTOR_HT_PROGRAM;
+  for(uint32_t t = 0; t < GPU_ACTOR_MAX_TYPES && all_prog; ++t)
   {
     const HostType& h = g.types[t];
     if(!h.created || reducible_ht(h.ht)) continue;
-    mask |= 1u << h.ht;
-    if(h.ht != GPU_ACTOR_HT_PROGRAM || h.prog_host.empty()) all_prog = false;
-    else progs.push_back({t, h.prog_host});
+    all_prog = !h.prog_host.empty();
+    key = jit::fnv1a(std::string(reinterpret_cast<const char*>(h.prog_host.data()), h.prog_host.size() * 8),
+                     jit::fnv1a(std::to_string(t), key));
   }
-  int kind = 0;
-  uint64_t want = jit::fnv1a(z12 ? "z12" : "z11");
-  if(all_prog && !progs.empty() && g.split_plan)
+  if(all_prog && split_plan)
   {
-    kind = 1;
-    for(const jit::Prog& p : progs)
-      want = jit::fnv1a(std::string(reinterpret_cast<const char*>(p.code.data()), p.code.size() * 8),
-                        jit::fnv1a(std::to_string(p.type), want));
+    p.jit_kind = 1;
+    p.jit_key = key;
   }
-  else if(se.kernel == step_entry_for_any(z12).kernel && mask)
+  else if(se.kernel == step_entry(-1, z12).kernel && p.jit_mask)
   {
-    kind = 2;
-    want = jit::fnv1a("mix" + std::to_string(mask), want);
+    p.jit_kind = 2;
+    p.jit_key = jit::fnv1a("mix" + std::to_string(p.jit_mask), geo);
   }
-  if(!kind) return 0;
-  if(g.jit.mod && g.jit_set == want) return kind;
-  if(g.jit_failed == want) return 0;
+  g.plan = p;
+}
+
+// The plan's run-time compiled module, built or loaded once per set (a set
+// whose build fails stays on the compiled-in kernels; one seen before in this
+// process, or on disk, loads at once), with this engine's constants in it.
+bool jit_load(const StepPlan& p)
+{
+  if(g.jit.mod && g.jit_set == p.jit_key) return true;
+  if(g.jit_failed == p.jit_key) return false;
   jit::unload(g.jit);
   hipDeviceProp_t prop;
-  if(hipGetDeviceProperties(&prop, g.device) != hipSuccess) { (void)hipGetLastError(); return 0; }
+  if(hipGetDeviceProperties(&prop, g.device) != hipSuccess) { (void)hipGetLastError(); return false; }
   std::string arch = prop.gcnArchName;
   arch = arch.substr(0, arch.find(':'));
+  const bool z12 = g.zbits == 12;
   std::string log;
-  const int rc = kind == 1 ? jit::build(progs, z12, arch, g.jit, log)
-                           : jit::build_mix(mask, z12, arch, g.jit, log);
+  int rc;
+  if(p.jit_kind == 1)
+  {
+    std::vector<jit::Prog> progs;
+    for(uint32_t t = 0; t < GPU_ACTOR_MAX_TYPES; ++t)
+      if(g.types[t].created && !reducible_ht(g.types[t].ht)) progs.push_back({t, g.types[t].prog_host});
+    rc = jit::build(progs, z12, arch, g.jit, log);
+  }
+  else
+    rc = jit::build_mix(p.jit_mask, z12, arch, g.jit, log);
   if(getenv("PONYC_AMD_JIT_LOG"))
-    fprintf(stderr, "gpu_actor jit: %s %s%s (rc %d) %s\n", kind == 1 ? "programs" : "mix",
-            kind == 2 ? ("mask " + std::to_string(mask) + " ").c_str() : "", z12 ? "z12" : "z11", rc,
+    fprintf(stderr, "gpu_actor jit: %s %s%s (rc %d) %s\n", p.jit_kind == 1 ? "programs" : "mix",
+            p.jit_kind == 2 ? ("mask " + std::to_string(p.jit_mask) + " ").c_str() : "", z12 ? "z12" : "z11", rc,
             log.c_str());
   if(rc != 0)
   {
-    g.jit_failed = want;
-    return 0;
+    g.jit_failed = p.jit_key;
+    return false;
   }
-  g.jit_set = want;
+  g.jit_set = p.jit_key;
   g.jit_builds++;
   if(hipMemcpyHtoDAsync(g.jit.types, g.td_host, sizeof(g.td_host), g.stream) != hipSuccess ||
      hipMemcpyHtoDAsync(g.jit.eng, &g.eng_host, sizeof(g.eng_host), g.stream) != hipSuccess)
   {
     (void)hipGetLastError();
     jit::unload(g.jit);
-    g.jit_failed = want;
-    return 0;
+    g.jit_failed = p.jit_key;
+    return false;
   }
-  return kind;
+  return true;
 }
 
-int launch_step(uint32_t slot, hipEvent_t e0, hipEvent_t e1)
+// Whether the step runs the plan's run-time compiled module: it is wanted,
+// it builds, and its static LDS leaves room for the bucket arrays. Asked at
+// the first launch under a plan; the answer stands until the next plan.
+bool jit_ready()
+{
+  StepPlan& p = g.plan;
+  if(!p.jit_kind || !g.consts_host) return false;
+  if(!p.jit_asked)
+  {
+    p.jit_asked = true;
+    p.jit_ok = jit_load(p) && g.jit.static_lds + p.dyn <= kLdsPerWorkgroup;
+  }
+  return p.jit_ok;
+}
+
+int step_after_launch(uint32_t slot);
+
+// One superstep: the plan's launches on parity g.par (+ exchange), then flip
+// parity.
+int launch_step(uint32_t slot)
 {
   if(g.n_zones == 0) return 0;
   g.dev_epoch++;
-  const StepEntry se = pick_step_entry();
-  if(se.stub) return GPU_ACTOR_EINVAL;      // an experiment build without this table
+  const StepPlan& p = g.plan;
+  const StepEntry& se = p.entry;
+  if(p.stub) return GPU_ACTOR_EINVAL;       // an experiment build without this table
   if(g.land8) g.land8_dirty = true;
-  // bucket arrays (4 x buckets — an order-free zone's two passes need no
-  // more: zone_dev.h two_pass; six for a message-local table's, dp_table)
-  // and, for hot receivers, the sort's work area
-  const uint64_t nb = g.n_zones + (R() > 1 ? R() : 0);
-  if(!step_fits(se, nb)) return GPU_ACTOR_ERANGE;    // more buckets than a workgroup's LDS holds
-  const size_t dyn = step_dyn_bytes(se, nb);
+  if(!p.fits) return GPU_ACTOR_ERANGE;      // more buckets than a workgroup's LDS holds
   // an engine with host ports: this step's place in the keys of the messages
   // it sends out (send_host reads it), counted from the first step since the
   // last collection
@@ -2544,79 +2579,38 @@ int launch_step(uint32_t slot, hipEvent_t e0, hipEvent_t e1)
       (uint64_t)(g.sidx - g.host_base) << g.host_kshift);
     HIPCK(hipGetLastError());
   }
-  // the run-time compiled step (jit_ensure), when it builds and fits: the
-  // programs' as two launches like the interpreter's, or a mix's one launch
-  // with k_hot before it where hot zones are prepared
-  g.jit_used = false;
-  const int jk = jit_ensure(se);
-  if(jk && g.jit.static_lds + dyn <= kLdsPerWorkgroup)
-  {
-    g.jit_used = true;
-    uint32_t a_cur = g.par, a_slot = slot, a_sidx = g.sidx;
-    void* args[] = {&a_cur, &a_slot, &a_sidx};
-    if(e0) HIPCK(hipEventRecord(e0, g.stream));
-    if(jk == 2 && g.hot_on)
-      hipLaunchKernelGGL(k_hot, dim3(kHotBlocks), dim3(kHotThreads), 5u * zone_actors() * sizeof(uint32_t),
-        g.stream, g.par, g.sidx);
-    HIPCK(hipModuleLaunchKernel(g.jit.plan, g.n_zones, 1, 1, se.threads, 1, 1, (unsigned)dyn, g.stream,
-      args, nullptr));
-    if(jk == 1)
-      HIPCK(hipModuleLaunchKernel(g.jit.rest, g.n_zones, 1, 1, se.threads, 1, 1, (unsigned)dyn, g.stream,
-        args, nullptr));
-    if(g.defer_big)
-      hipLaunchKernelGGL(k_carry_big, dim3(kBigCopyBlocks), dim3(kBlock), 0, g.stream, g.par);
-    const int grc = gups_apply_launch(nullptr);
-    if(grc) return grc;
-    // (n_ranks > 1 with listed GUPS chunks: the end event goes behind their
-    // apply, gups_gather_apply)
-    if(e1 && !(g.gups_type >= 0 && R() > 1)) HIPCK(hipEventRecord(e1, g.stream));
-    return step_after_launch(slot, e0, e1);
-  }
-  // a two-pass table's step as two launches: its two-pass zones, then the rest
-  // (zone_dev.h k_step PM)
-  // (fused: one launch of PM 3 in their place)
-  const bool fused = se.plan && g.split_plan && g.fuse && se.fused;
-  const bool split = se.plan && g.split_plan && !fused;
-  step_kernel_t kern = fused ? se.fused : split ? se.plan : se.kernel;
   // hot zones first (hot_dev.h): the whole GPU prepares them for k_step
   const size_t hot_lds = 5u * zone_actors() * sizeof(uint32_t);
-  if(e0)
+  // the run-time compiled step: the programs' as two launches like the
+  // interpreter's, or a mix's one launch with k_hot before it where hot zones
+  // are prepared
+  g.jit_used = jit_ready();
+  if(g.jit_used)
   {
-    // the events take the dispatch's own start/end timestamps: no marker
-    // packets between steps (the chunks' apply ends them: the next launch
-    // here on one rank, gups_gather_apply's after the exchange otherwise)
-    const bool gups = g.gups_type >= 0;
-    const bool more = split || g.defer_big || gups;
-    if(g.hot_on)
-      hipExtLaunchKernelGGL(k_hot, dim3(kHotBlocks), dim3(kHotThreads), (uint32_t)hot_lds, g.stream,
-        e0, nullptr, 0u, g.par, g.sidx);
-    hipExtLaunchKernelGGL(kern, dim3(g.n_zones), dim3(se.threads), (uint32_t)dyn, g.stream,
-      g.hot_on ? nullptr : e0, more ? nullptr : e1, 0u, g.par, slot, g.sidx);
-    if(split)
-      hipExtLaunchKernelGGL(se.rest, dim3(g.n_zones), dim3(se.threads), (uint32_t)dyn, g.stream,
-        nullptr, (g.defer_big || gups) ? nullptr : e1, 0u, g.par, slot, g.sidx);
-    if(g.defer_big)
-      hipExtLaunchKernelGGL(k_carry_big, dim3(kBigCopyBlocks), dim3(kBlock), 0, g.stream,
-        nullptr, gups ? nullptr : e1, 0u, g.par);
-    HIPCK(hipGetLastError());
-    const int grc = gups_apply_launch(e1);
-    if(grc) return grc;
+    uint32_t a_cur = g.par, a_slot = slot, a_sidx = g.sidx;
+    void* args[] = {&a_cur, &a_slot, &a_sidx};
+    if(p.jit_kind == 2 && g.hot_on)
+      hipLaunchKernelGGL(k_hot, dim3(kHotBlocks), dim3(kHotThreads), hot_lds, g.stream, g.par, g.sidx);
+    HIPCK(hipModuleLaunchKernel(g.jit.plan, g.n_zones, 1, 1, se.threads, 1, 1, (unsigned)p.dyn, g.stream,
+      args, nullptr));
+    if(p.jit_kind == 1)
+      HIPCK(hipModuleLaunchKernel(g.jit.rest, g.n_zones, 1, 1, se.threads, 1, 1, (unsigned)p.dyn, g.stream,
+        args, nullptr));
   }
   else
   {
     if(g.hot_on)
       hipLaunchKernelGGL(k_hot, dim3(kHotBlocks), dim3(kHotThreads), hot_lds, g.stream, g.par, g.sidx);
-    hipLaunchKernelGGL(kern, dim3(g.n_zones), dim3(se.threads), dyn, g.stream, g.par, slot, g.sidx);
-    if(split)
-      hipLaunchKernelGGL(se.rest, dim3(g.n_zones), dim3(se.threads), dyn, g.stream, g.par, slot, g.sidx);
-    if(g.defer_big)
-      hipLaunchKernelGGL(k_carry_big, dim3(kBigCopyBlocks), dim3(kBlock), 0, g.stream, g.par);
-    HIPCK(hipGetLastError());
-    const int grc = gups_apply_launch(nullptr);
-    if(grc) return grc;
+    hipLaunchKernelGGL(p.first, dim3(g.n_zones), dim3(se.threads), p.dyn, g.stream, g.par, slot, g.sidx);
+    if(p.second)
+      hipLaunchKernelGGL(p.second, dim3(g.n_zones), dim3(se.threads), p.dyn, g.stream, g.par, slot, g.sidx);
   }
+  if(g.defer_big)
+    hipLaunchKernelGGL(k_carry_big, dim3(kBigCopyBlocks), dim3(kBlock), 0, g.stream, g.par);
   HIPCK(hipGetLastError());
-  return step_after_launch(slot, e0, e1);
+  const int grc = gups_apply_launch();
+  if(grc) return grc;
+  return step_after_launch(slot);
 }
 
 // n_ranks > 1, behind a step that ran: every rank's packed GUPS chunks
@@ -2624,8 +2618,8 @@ int launch_step(uint32_t slot, hipEvent_t e0, hipEvent_t e1)
 // gathered in rank order — one 8-byte PolyRand state per chunk, through the
 // grouped send/recv that gathers spawn records — and applied by
 // k_gups_apply_ranks. A rank that owns no updater takes part in the gather
-// and launches nothing. The step's end event, when given, ends here.
-int gups_gather_apply(hipEvent_t e1)
+// and launches nothing.
+int gups_gather_apply()
 {
   const uint32_t n = R();
   const unsigned long long* cnt = g.h_xc + 2 * n + 3;
@@ -2645,7 +2639,6 @@ int gups_gather_apply(hipEvent_t e1)
     HIPCK(hipStreamSynchronize(g.stream));      // no k_gups_apply_ranks still reads the old one
     HIPCK(g.d_gups_all.alloc(cap));
   }
-  bool launched = false;
   if(total)
   {
     if(mine)
@@ -2669,24 +2662,18 @@ int gups_gather_apply(hipEvent_t e1)
     {
       const uint64_t per_block = 4ull * (64u / g.gups_parts);
       const uint32_t blocks = (uint32_t)std::min<uint64_t>((total + per_block - 1) / per_block, kGupsBlocks);
-      if(e1)
-        hipExtLaunchKernelGGL(k_gups_apply_ranks, dim3(blocks), dim3(256), 0, g.stream, nullptr, e1, 0u,
-          (const uint64_t*)g.d_gups_all, total, off[rank()], mine);
-      else
-        hipLaunchKernelGGL(k_gups_apply_ranks, dim3(blocks), dim3(256), 0, g.stream,
-          (const uint64_t*)g.d_gups_all, total, off[rank()], mine);
+      hipLaunchKernelGGL(k_gups_apply_ranks, dim3(blocks), dim3(256), 0, g.stream,
+        (const uint64_t*)g.d_gups_all, total, off[rank()], mine);
       HIPCK(hipGetLastError());
-      launched = true;
     }
   }
-  if(e1 && !launched) HIPCK(hipEventRecord(e1, g.stream));
   return 0;
 }
 
 // After a step's launches: the parity and step index advance; the exchange
 // (n_ranks > 1), the halted step's rerun, the GUPS chunks' gather and apply
 // (n_ranks > 1), spawned actors.
-int step_after_launch(uint32_t slot, hipEvent_t e0, hipEvent_t e1)
+int step_after_launch(uint32_t slot)
 {
   HIPCK(hipGetLastError());
   const uint32_t step_sidx = g.sidx;
@@ -2706,11 +2693,11 @@ int step_after_launch(uint32_t slot, hipEvent_t e0, hipEvent_t e1)
       g.sidx--;
       rc = pend_clear(slot, 1);
       if(rc) return rc;
-      return launch_step(slot, e0, e1);
+      return launch_step(slot);
     }
     if(g.gups_type >= 0)
     {
-      rc = gups_gather_apply(e1);
+      rc = gups_gather_apply();
       if(rc) return rc;
     }
   }
@@ -3380,7 +3367,7 @@ int run_sparse(uint64_t max_steps, SparseCtl& out)
   HIPCK(hipGetLastError());
   {
     // the chunks its supersteps listed (2^16 or more per segment)
-    const int rc = gups_apply_launch(nullptr);
+    const int rc = gups_apply_launch();
     if(rc) return rc;
   }
   HIPCK(hipMemcpyAsync(g.h_ctl, g.d_ctl, sizeof(SparseCtl), hipMemcpyDeviceToHost, g.stream));
@@ -3414,6 +3401,18 @@ int pending_now(unsigned long long& out)
 // decision is this status summed over ranks (k_spill_local + pend_read, a
 // collective every rank makes at the same point), so all ranks run
 // fixup_spill — and clear their spill flags — together or none does.
+// This rank's spill status into pend[first + n - 1] (k_spill_local) and its
+// SpillStat into h_sstat, then pend[first .. first + n) summed over ranks
+// (pend_read: the collective, which also synchronises the stream).
+int spill_sum_read(uint32_t first, uint32_t n, std::vector<unsigned long long>& pv)
+{
+  hipLaunchKernelGGL(k_spill_local, dim3(1), dim3(1), 0, g.stream, g.d_pend + first + n - 1);
+  HIPCK(hipGetLastError());
+  HIPCK(hipMemcpyAsync(g.h_sstat, g.d_sstat, sizeof(SpillStat), hipMemcpyDeviceToHost,
+    g.stream));
+  return pend_read(first, n, pv);
+}
+
 int settle_spills()
 {
   if(R() == 1)
@@ -3424,12 +3423,8 @@ int settle_spills()
     if(rc) return rc;
     return spill_pending() ? fixup_spill() : 0;
   }
-  hipLaunchKernelGGL(k_spill_local, dim3(1), dim3(1), 0, g.stream, g.d_pend + kPendPre);
-  HIPCK(hipGetLastError());
-  HIPCK(hipMemcpyAsync(g.h_sstat, g.d_sstat, sizeof(SpillStat), hipMemcpyDeviceToHost,
-    g.stream));
   std::vector<unsigned long long> pv;
-  const int rc = pend_read(kPendPre, 1, pv);
+  const int rc = spill_sum_read(kPendPre, 1, pv);
   if(rc) return rc;
   return pv[0] ? fixup_spill() : 0;
 }
@@ -3499,7 +3494,7 @@ int run_locked(uint64_t max_steps, uint64_t* steps_done)
       {
         par_at[j] = g.par;
         sidx_at[j] = g.sidx;
-        rc = launch_step(j, nullptr, nullptr);
+        rc = launch_step(j);
         if(rc) return rc;
       }
       par_at[k] = g.par;
@@ -3507,11 +3502,7 @@ int run_locked(uint64_t max_steps, uint64_t* steps_done)
       if(rc) return rc;
       // pend[k + 1]: the spill status, summed over ranks with the counts, so
       // every rank takes the same branch below (one rank: its own status)
-      hipLaunchKernelGGL(k_spill_local, dim3(1), dim3(1), 0, g.stream, g.d_pend + k + 1);
-      HIPCK(hipGetLastError());
-      HIPCK(hipMemcpyAsync(g.h_sstat, g.d_sstat, sizeof(SpillStat), hipMemcpyDeviceToHost,
-        g.stream));
-      rc = pend_read(0, k + 2, pv);
+      rc = spill_sum_read(0, k + 2, pv);
       if(rc) return rc;
       uint32_t j = 0;
       bool halted = false;
@@ -3663,7 +3654,7 @@ GPU_ACTOR_API int gpu_actor_run_fixed(uint64_t n)
     HIPCK(hipEventRecord(g.ev[0], g.stream));
     for(uint64_t j = 0; j < left; ++j)
     {
-      rc = launch_step((uint32_t)(j % kPendPre), nullptr, nullptr);
+      rc = launch_step((uint32_t)(j % kPendPre));
       if(rc) return rc;
     }
     HIPCK(hipEventRecord(g.ev[1], g.stream));
@@ -3685,12 +3676,8 @@ GPU_ACTOR_API int gpu_actor_run_fixed(uint64_t n)
     else
     {
       // the same decision on every rank (see settle_spills)
-      hipLaunchKernelGGL(k_spill_local, dim3(1), dim3(1), 0, g.stream, g.d_pend + kPendPre);
-      HIPCK(hipGetLastError());
-      HIPCK(hipMemcpyAsync(g.h_sstat, g.d_sstat, sizeof(SpillStat), hipMemcpyDeviceToHost,
-        g.stream));
       std::vector<unsigned long long> pv;
-      rc = pend_read(kPendPre, 1, pv);       // synchronises the stream
+      rc = spill_sum_read(kPendPre, 1, pv);  // synchronises the stream
       if(rc) return rc;
       any = pv[0] != 0;
     }

@@ -35,7 +35,26 @@ namespace gpa {
 
 constexpr int      kBlock = 256;                 // helper kernels
 constexpr int      kWaves = kBlock / 64;
-// Zone geometry (A/B builds override it: scripts/build_variants.sh)
+// Zone geometry (A/B builds override it: scripts/build_variants.sh). GPA_Z12 is
+// the one switch to the second geometry the library holds — 4096-actor zones,
+// 1024-thread workgroups, with the index budget and the scatter tile of
+// zone_dev.h sized for them: the compiled-in step_*_z12.hip units (step_tu.h)
+// and the run-time compiled ones (jit_host.h) set it and nothing else, so both
+// see one layout. Each value can still be overridden on its own.
+#ifdef GPA_Z12
+#ifndef GPA_ZONE_BITS
+#define GPA_ZONE_BITS 12
+#endif
+#ifndef GPA_ZONE_THREADS
+#define GPA_ZONE_THREADS 1024
+#endif
+#ifndef GPA_IDX_CAP
+#define GPA_IDX_CAP 24576
+#endif
+#ifndef GPA_TILE
+#define GPA_TILE 7168
+#endif
+#endif
 #ifndef GPA_ZONE_BITS
 #define GPA_ZONE_BITS 11
 #endif

@@ -158,9 +158,7 @@ inline std::string unit_source(const std::vector<Prog>& progs, bool z12)
     for(size_t k = 0; k < p.code.size(); ++k)       // (a jump may run the entry words too)
       yields |= (p.code[k] & 0xFFu) == GPU_ACTOR_OP_YIELD;
   s += std::string("#define GPA_JIT_YIELD ") + (yields ? "1" : "0") + "\n";
-  if(z12)
-    s += "#define GPA_ZONE_BITS 12\n#define GPA_ZONE_THREADS 1024\n#define GPA_IDX_CAP 24576\n"
-         "#define GPA_TILE 7168\n";
+  if(z12) s += "#define GPA_Z12 1\n";        // the 4096-actor zone geometry (engine_dev.h)
   s += "#include \"zone_dev.h\"\nnamespace gpa {\n";
   // A program's SEND is send_program (engine_dev.h: a host port's id goes to
   // send_host, every other target to send_serial). The generated functions
@@ -188,9 +186,7 @@ inline std::string mix_source(uint32_t mask, bool z12)
 {
   std::string s = "// generated by engine.hip jit (jit_host.h)\n#define GPA_STEP_TU 1\n";
   s += "#define GPA_MIX_MASK " + std::to_string(mask) + "u\n";
-  if(z12)
-    s += "#define GPA_ZONE_BITS 12\n#define GPA_ZONE_THREADS 1024\n#define GPA_IDX_CAP 24576\n"
-         "#define GPA_TILE 7168\n";
+  if(z12) s += "#define GPA_Z12 1\n";        // the 4096-actor zone geometry (engine_dev.h)
   s += "#include \"zone_dev.h\"\nnamespace gpa {\n"
        "template __global__ void k_step<-1, 0>(uint32_t, uint32_t, uint32_t);\n}\n";
   return s;

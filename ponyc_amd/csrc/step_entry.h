@@ -1,17 +1,39 @@
-// step_entry.h — the compiled instantiations of k_step (zone_dev.h).
+// step_entry.h — the compiled instantiations of k_step (zone_dev.h), listed
+// once: GPA_STEP_TABLES below. The declarations here, the host's table of
+// entries and its lookup (engine.hip: step_rows, step_entry) and the check of
+// every unit against the list (step_tu.h) are generated from it.
 //
-// Each instantiation lives in a translation unit of its own (step_*.hip), so
-// the library builds them in parallel; each such unit is its own code object
-// with its own copy of the engine constants (c_types, c_eng), which the host
-// uploads to every unit (engine.hip: upload_types).
+// Each instantiation lives in a translation unit of its own (step_<name>.hip),
+// so the library builds them in parallel; each such unit is its own code
+// object with its own copy of the engine constants (c_types, c_eng), which the
+// host uploads to every entry of the table (engine.hip: upload_types).
 //
 // Two zone geometries are compiled: 2048-actor zones with 512-thread
-// workgroups (namespace gpa, step_*.hip) and 4096-actor zones with 1024-thread
-// workgroups (namespace gpa_z12, step_*_z12.hip: the same sources with the
-// namespace renamed). The host picks one per engine (engine.hip: relayout_zones).
+// workgroups (namespace gpa, step_<name>.hip) and 4096-actor zones with
+// 1024-thread workgroups (namespace gpa_z12, step_<name>_z12.hip: the same
+// unit behind step_tu.h's GPA_STEP_Z12). The host picks one per engine
+// (engine.hip: relayout_zones).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "../../include/gpu_actor.h"
+
+// X(name, handler table): the unit step_<name>.hip exports step_entry_<name>(),
+// whose kernel is k_step<handler table>. The table is a preprocessor integer
+// (step_tu.h and engine_dev.h test it in #if): -1 is any mix of tables, 64 the
+// FIFO sources + sinks pair (zone_dev.h kHtFifoPair).
+#define GPA_STEP_TABLES(X)                       \
+  X(any, -1)                                     \
+  X(ring, GPU_ACTOR_HT_RING)                     \
+  X(pinger, GPU_ACTOR_HT_PINGER)                 \
+  X(pinger_det, GPU_ACTOR_HT_PINGER_DET)         \
+  X(fanin_sender, GPU_ACTOR_HT_FANIN_SENDER)     \
+  X(gups_streamer, GPU_ACTOR_HT_GUPS_STREAMER)   \
+  X(storm, GPU_ACTOR_HT_STORM)                   \
+  X(spreader, GPU_ACTOR_HT_SPREADER)             \
+  X(fifo_pair, 64)                               \
+  X(program, GPU_ACTOR_HT_PROGRAM)
 
 typedef void (*step_kernel_t)(uint32_t, uint32_t, uint32_t);
 
@@ -37,17 +59,14 @@ struct StepEntry {
   uint64_t plan_arg;
 };
 
-namespace gpa {
+// the handler table of each name, for step_tu.h's check of its unit
+enum : int {
+#define GPA_STEP_X(name, ht) kStepHt_##name = (ht),
+  GPA_STEP_TABLES(GPA_STEP_X)
+#undef GPA_STEP_X
+};
 
-StepEntry step_entry_any();             // any mix of handler tables
-StepEntry step_entry_ring();
-StepEntry step_entry_pinger();
-StepEntry step_entry_pinger_det();
-StepEntry step_entry_fanin_sender();
-StepEntry step_entry_gups_streamer();
-StepEntry step_entry_storm();
-StepEntry step_entry_spreader();
-StepEntry step_entry_fifo_pair();       // FIFO sources + sinks (zone_dev.h kHtFifoPair)
-StepEntry step_entry_program();         // behaviours as programs (GPU_ACTOR_HT_PROGRAM)
-
-} // namespace gpa
+#define GPA_STEP_X(name, ht) StepEntry step_entry_##name();
+namespace gpa { GPA_STEP_TABLES(GPA_STEP_X) }
+namespace gpa_z12 { GPA_STEP_TABLES(GPA_STEP_X) }
+#undef GPA_STEP_X

@@ -1,9 +1,5 @@
-// k_step<GPU_ACTOR_HT_STORM> at 4096-actor zones, 1024-thread workgroups (step_entry.h).
-#define GPA_ZONE_BITS 12
-#define GPA_ZONE_THREADS 1024
-#define GPA_IDX_CAP 24576
-#define GPA_TILE 7168
-#define gpa gpa_z12
+// k_step<GPU_ACTOR_HT_STORM> at 4096-actor zones, 1024-thread workgroups (step_tu.h).
+#define GPA_STEP_Z12 1
+#define GPA_STEP_NAME storm
 #define GPA_STEP_HT GPU_ACTOR_HT_STORM
-#define GPA_STEP_ENTRY step_entry_storm
 #include "step_tu.h"

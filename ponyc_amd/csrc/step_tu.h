@@ -1,11 +1,26 @@
-// step_tu.h — body of one k_step translation unit (step_*.hip): instantiates
-// k_step<GPA_STEP_HT> and exports it with the upload of this code object's
-// engine constants. A step_*_z12.hip unit first sets the 4096-actor zone
-// geometry and renames the namespace (gpa -> gpa_z12), so both geometries'
-// kernels link into one library.
+// step_tu.h — body of one k_step translation unit (step_<name>.hip). The unit
+// names its row of step_entry.h's GPA_STEP_TABLES — GPA_STEP_NAME and, as a
+// preprocessor integer, GPA_STEP_HT — and this header instantiates
+// k_step<GPA_STEP_HT> and exports it as step_entry_<name>() with the upload of
+// this code object's engine constants. A step_<name>_z12.hip unit sets
+// GPA_STEP_Z12 before: the 4096-actor zone geometry (engine_dev.h GPA_Z12) and
+// the namespace renamed (gpa -> gpa_z12), so both geometries' kernels link
+// into one library.
 #define GPA_STEP_TU 1
+#ifdef GPA_STEP_Z12
+#define GPA_Z12 1
+#define gpa gpa_z12
+#endif
 #include "zone_dev.h"
 #include "step_entry.h"
+
+#define GPA_STEP_CAT_(a, b) a##b
+#define GPA_STEP_CAT(a, b) GPA_STEP_CAT_(a, b)
+// a unit that is not in the table, or under another handler table, does not compile
+static_assert(GPA_STEP_CAT(kStepHt_, GPA_STEP_NAME) == (GPA_STEP_HT),
+              "GPA_STEP_NAME / GPA_STEP_HT is not a row of GPA_STEP_TABLES (step_entry.h)");
+static_assert(kStepHt_fifo_pair == gpa::kHtFifoPair, "GPA_STEP_TABLES' fifo_pair row");
+#define GPA_STEP_ENTRY GPA_STEP_CAT(step_entry_, GPA_STEP_NAME)
 
 namespace gpa {
 

@@ -46,6 +46,8 @@ def sets():
     # both geometries
     from mixed_worlds import mix_units
     out += mix_units()
+    # pingers + a ring (tests/test_gpu_step_plan.py), at both geometries
+    out += [((1 << 1) | (1 << 2), z12) for z12 in (False, True)]
     return out
 
 

@@ -110,7 +110,7 @@ class World:
 
     def mask(self):
         """The mix a run-time compiled any-mix step of this world holds
-        (engine.hip jit_ensure): a bit per table of its serial actors."""
+        (engine.hip plan_step): a bit per table of its serial actors."""
         m = 0
         for p in self.parts:
             for ht in p.tables:

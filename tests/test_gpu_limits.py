@@ -320,7 +320,7 @@ def test_spawn_high_seq(engine_factory, oracle, monkeypatch, sink, jit):
     seq) order: child j's constructor argument names its parent and ordinal.
     sink "fifo": the compiled HT_FIFO_SINK table; the engine is then a mix of
     tables, and PONYC_AMD_JIT=1 means the any-mix kernel built for this mix
-    (engine.hip jit_ensure, kind 2), in which the spawner still runs in the
+    (engine.hip plan_step, kind 2), in which the spawner still runs in the
     interpreter. sink "program": the same fold as a program, so every serial
     actor runs a program and PONYC_AMD_JIT=1 runs the step generated from the
     programs (kind 1): SPAWN and SEND at high seq in compiled program code."""
